@@ -5,7 +5,11 @@ fp32-class mode that meets the north star's 1e-3 logit bar (the reference comput
 PromptSRC/clip/model.py:699). The fp16 mode (|d logit| 0.026, outside that bar) is reported
 beside it as context (``fp16``).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    (a plain run sets up, warms up, times the K steps and prints the line: metric, value,
+     ms_per_step, dtype, config. --dump-outputs DIR writes what the last timed step computed -- the
+     loss, the updated prompt parameters and their gradients -- as DIR/<name>.npy; the inputs are
+     seeded, the same in every run. Everything else listed below is measured under --full only.)
     (N > 1 without a torchrun environment: this process starts
      python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...
      bench.py ... as a child -- before anything touches the GPU -- relays its output and exits
@@ -17,7 +21,7 @@ cosine logits -> CE -> RCCL all-reduce of the prompt grads (N>1) -> fused SGD st
 Weak scaling: every rank processes its own B images (value = total images over all ranks /
 max-over-ranks time). Weights are the seeded synthetic CLIP (no network).
 
-The JSON line also carries (rank 0, N=1 unless noted):
+Under --full the JSON line also carries (rank 0, N=1 unless noted):
 * ``roofline``: the dominant kernel of the step (by time) with its algorithmic FLOPs / bytes
   per launch over its average launch time, both from hipEvents recorded around every launch
   site (clipk_prof_sites_*) during --prof-steps extra steps run right after the timed ones
@@ -366,11 +370,12 @@ def build_trainer(args, prec, batch, dev, rank, n_test=0, n_test_device=0, class
     return trainer, dm
 
 
-def time_train(trainer, dm, steps, warmup, batch=None, prof_steps=0):
+def time_train(trainer, dm, steps, warmup, batch=None, prof_steps=0, after_timed=None):
     """Warm-up, then `steps` timed steps (barrier + synchronize both sides, max over ranks);
     then, when prof_steps > 0, that many more steps with hipEvents around every launch
     site (kept out of the timed region: ~300 event records per step add ~15 % wall time),
-    returning the per-site table."""
+    returning the per-site table. after_timed(summary): called with the last timed step's
+    return value once the clock has stopped, before any profiled step changes the prompts."""
     import torch
     from fsp_amd import dist, _native as N
     batches = dm.train_loader_x
@@ -387,11 +392,14 @@ def time_train(trainer, dm, steps, warmup, batch=None, prof_steps=0):
     torch.cuda.synchronize()
     dist.barrier()
     t0 = time.perf_counter()
+    last = None
     for i in range(steps):
-        step(i)
+        last = step(i)
     torch.cuda.synchronize()
     dist.barrier()
     t = time.perf_counter() - t0
+    if after_timed is not None:
+        after_timed(last)
     table = None
     if prof_steps > 0:
         lib = N.load()
@@ -402,6 +410,41 @@ def time_train(trainer, dm, steps, warmup, batch=None, prof_steps=0):
         table = N.prof_sites_read()
         lib.clipk_prof_sites_enable(0)
     return dist.max_over_ranks(t), table
+
+
+DUMP_BUDGET = 64 << 20  # bytes of --dump-outputs files in all
+
+
+def step_outputs(trainer, summary):
+    """What a caller of the timed path holds after a step, as {name: host array}: the loss
+    summary forward_backward returned, and the prompt learner's trainable parameters as the
+    step's SGD update left them, with the gradients it applied. A deferred overflow check of
+    that step (CoCoOp fp32s) is settled first, so the parameters are the updated ones."""
+    if hasattr(trainer, "flush_deferred"):
+        trainer.flush_deferred()
+    out = {k: v for k, v in (summary or {}).items()}
+    for name, p in trainer.model.prompt_learner.named_parameters():
+        if p.requires_grad:
+            out["param." + name] = p.detach().float().cpu().numpy()
+            if p.grad is not None:
+                out["grad." + name] = p.grad.detach().float().cpu().numpy()
+    return out
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET):
+    """Write {name: array} as dirname/<name>.npy in float32 (float64 arrays stay float64), at
+    most `budget` bytes of data in all: an array over its equal share of the budget is stored as a
+    fixed, seeded sample of its flattened elements (the same indices in every run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def time_eval(trainer, dm, n_images):
@@ -561,7 +604,17 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE config 4 / 5 lines")
     ap.add_argument("--weights", choices=("fp16", "fp32"), default="fp16",
                     help="synthetic CLIP weights rounded to fp16 (as the released checkpoints) or fp32")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline train step: its per-site roofline steps, the eval timing, the "
+                         "batch-1 / CoOp / other-precision / config 4 and 5 lines and the CPU baseline "
+                         "(each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, updated prompt "
+                         "parameters, their gradients) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_prof = args.no_extra = args.no_configs = args.no_cpu_baseline = True
+        args.eval_images = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one rank per GPU: torchrun as a CHILD process (this process has not touched the GPU)
@@ -587,17 +640,23 @@ def main():
     n_eval_rank = dist.shard_range(args.eval_images)[1] - dist.shard_range(args.eval_images)[0]
 
     log(f"headline: {args.arch} B={args.batch} C={args.classes} {args.prec}")
+    torch.manual_seed(0)  # the Meta-Net's nn.Linear initialisation: the same start in every run
     trainer, dm = build_trainer(args, args.prec, args.batch, dev, rank, n_test_device=n_eval_rank)
     lay = trainer.model.prompt_learner.layout
     L = lay.L
     n_prof = 0 if args.no_prof else args.prof_steps
-    t, sites = time_train(trainer, dm, args.steps, args.warmup, prof_steps=n_prof)
+    dumped = {}
+    t, sites = time_train(trainer, dm, args.steps, args.warmup, prof_steps=n_prof,
+                          after_timed=(lambda s: dumped.update(step_outputs(trainer, s))) if args.dump_outputs else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dumped)
     pk = peak_key(args.prec, trainer)
     table = kernel_table(sites, n_prof, pk) if sites else None
     roof = roofline_of(table, pk) if table else None
-    log(f"headline train {1000 * t / args.steps:.3f} ms/step; eval")
-    eval_ips, n_eval = time_eval(trainer, dm, n_eval_rank)
-    log(f"eval {eval_ips:.1f} img/s")
+    log(f"headline train {1000 * t / args.steps:.3f} ms/step")
+    if args.full:
+        eval_ips, n_eval = time_eval(trainer, dm, n_eval_rank)
+        log(f"eval {eval_ips:.1f} img/s")
 
     f_img, f_txt, b_txt = flops(arch, args.classes, L)
     step_flops = args.batch * (f_img + args.classes * (f_txt + b_txt))
@@ -627,9 +686,7 @@ def main():
                    "vision": ("the NEXT batch's frozen ViT forward on a side stream (NATIVE.PREFETCH_VISION, "
                               "TrainerX.run_epoch's lookahead): one ViT fwd + one text fwd+bwd per step"
                               if trainer.cfg.NATIVE.get("PREFETCH_VISION", False) else "in line")},
-        "eval_images_per_sec": round(eval_ips, 3),
-        "eval_images": int(dist.sum_over_ranks(n_eval)),
-        "eval_note": "forward only, test batch 100, distinct resident images sharded over the ranks",
+        "full": args.full, "outputs_dumped": sorted(dumped) if args.dump_outputs else None,
         "source_digest": N.library_digest()[:16],
         # SURVEY §8(d) algorithmic FLOPs per second: the plain [B*C, L_eff] layout (L_eff = max EOT
         # + 1), the same at the reference's 77 tokens, and the GEMM FLOPs the step executes
@@ -647,7 +704,10 @@ def main():
     }
     if args.prec == "fp32s":
         out["split_mode"] = {"text": trainer.model.text_core.split_mode, "vision": trainer.model.image_encoder.split_mode}
-    if world > 1:  # the step's gradient all-reduce measured on its own (part of ms_per_step above)
+    if args.full:
+        out.update({"eval_images_per_sec": round(eval_ips, 3), "eval_images": int(dist.sum_over_ranks(n_eval)),
+                    "eval_note": "forward only, test batch 100, distinct resident images sharded over the ranks"})
+    if args.full and world > 1:  # the step's gradient all-reduce measured on its own (part of ms_per_step above)
         out["grad_allreduce"] = time_grad_allreduce(list(trainer.model.prompt_learner.parameters()))
     del trainer, dm
     torch.cuda.empty_cache()

@@ -48,6 +48,43 @@ def test_metric_label_follows_arch():
     assert "ViT-L/14@336px" in bench.metric_name("ViT-L/14@336px")
 
 
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: one <name>.npy per array in float32 (float64 kept), the same bytes in every
+    run; an array over its share of the budget is stored as a fixed sample of its elements."""
+    import numpy as np
+    rs = np.random.RandomState(0)
+    arrays = {"loss": 2.5, "param.ctx": rs.rand(4, 8).astype(np.float16), "grad.big": rs.rand(1000),
+              "count": np.arange(6, dtype=np.int64)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays, budget=4 * 800)  # share: 800 bytes per array
+    bench.dump_outputs(str(tmp_path / "b"), arrays, budget=4 * 800)
+    assert sorted(os.listdir(tmp_path / "a")) == ["count.npy", "grad.big.npy", "loss.npy", "param.ctx.npy"]
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")}
+    assert got["loss"].dtype == np.float64 and got["loss"].shape == () and got["loss"] == 2.5  # a Python float
+    assert got["param.ctx"].dtype == np.float32 and np.array_equal(got["param.ctx"], arrays["param.ctx"])
+    assert got["count"].dtype == np.float32 and np.array_equal(got["count"], np.arange(6))
+    big = got["grad.big"]
+    assert big.dtype == np.float64 and big.shape == (100,) and np.isin(big, arrays["grad.big"]).all()
+    assert sum(a.nbytes for a in got.values()) <= 4 * 800
+    for n in os.listdir(tmp_path / "a"):
+        assert (tmp_path / "a" / n).read_bytes() == (tmp_path / "b" / n).read_bytes()
+
+
+def test_step_outputs_names():
+    """The dumped arrays of a step: the loss summary, then each trainable prompt parameter and
+    its gradient (frozen parameters are left out)."""
+    import types
+    import torch
+    pl = torch.nn.Module()
+    pl.ctx = torch.nn.Parameter(torch.ones(2, 3))
+    pl.ctx.grad = torch.full((2, 3), 0.5)
+    pl.frozen = torch.nn.Parameter(torch.zeros(2), requires_grad=False)
+    flushed = []
+    tr = types.SimpleNamespace(model=types.SimpleNamespace(prompt_learner=pl), flush_deferred=lambda: flushed.append(1))
+    out = bench.step_outputs(tr, {"loss": 1.25})
+    assert flushed == [1] and sorted(out) == ["grad.ctx", "loss", "param.ctx"]
+    assert out["loss"] == 1.25 and out["param.ctx"].sum() == 6 and out["grad.ctx"].sum() == 3
+
+
 def test_kernel_table_bound_from_intensity():
     """Each kernel class's roofline bound comes from its own FLOP/byte ratio against the ridge
     point (peak / 8 TB/s), not a fixed label: a K = 512 GEMM whose bytes outweigh its FLOPs is

@@ -14,7 +14,7 @@ for round in 1 2; do
       *) L=$R/build_ab/$t/libclipk.so;;
     esac
     f=gpurun_out/ab_$(echo "$t" | tr -c 'A-Za-z0-9_\n' '_')_${round}.json
-    env $ENVS CLIPK_LIB=$L timeout -k 10 200 python -u bench.py --steps 20 --warmup 3 --no-extra --no-cpu-baseline \
+    env $ENVS CLIPK_LIB=$L timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 3 --no-extra --no-cpu-baseline \
       --eval-images 2000 > $f 2> gpurun_out/ab_err.log || exit 1
     tail -1 $f | python3 -c "
 import json,sys
