@@ -3,10 +3,6 @@
 #pragma once
 #include "common.h"
 
-#ifndef CLIPK_ATTN_SNT
-#define CLIPK_ATTN_SNT 0
-#endif
-
 namespace clipk {
 
 constexpr float kScale = 0.125f;  // 1/sqrt(64)
@@ -65,14 +61,10 @@ __device__ __forceinline__ void st16(float* __restrict__ p, const float* v) {
   for (int c = 0; c < 4; ++c)
     reinterpret_cast<f32x4*>(p)[c] = (f32x4){v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]};
 }
-// lane slice s of a 64-float head row: columns {kCs c + kSl s + e : c, e < 4}. Interleaved
-// (CLIPK_F32_IL=1, default): each f32x4 load of the 4 lanes of a row covers 64 contiguous
-// bytes; contiguous (0): lane s holds columns 16 s .. 16 s + 15. Every global and LDS row
+// lane slice s of a 64-float head row: columns {kCs c + kSl s + e : c, e < 4}. Interleaved:
+// each f32x4 load of the 4 lanes of a row covers 64 contiguous bytes. Every global and LDS row
 // access of the fp32 attention kernels uses this one map, so q / k / v / dO / o slices pair up.
-#ifndef CLIPK_F32_IL
-#define CLIPK_F32_IL 1
-#endif
-constexpr int kSl = CLIPK_F32_IL ? 4 : 16, kCs = CLIPK_F32_IL ? 16 : 4;
+constexpr int kSl = 4, kCs = 16;
 __device__ __forceinline__ void ld16x(const float* __restrict__ p, float* v) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -95,13 +87,12 @@ __device__ __forceinline__ void split_parts(float v, _Float16& hi, _Float16& lo)
 }
 // st16x in the pre-split operand form of a split GEMM's A (include/clipk.h CLIPK_A_SPLIT: per 8
 // consecutive columns 16 B of hi parts then 16 B of lo parts, 4 B per element as the fp32 row).
-// Called by all 4 lanes of a row (lane = 4 r + s, the slice map above, interleaved only): chunk c
+// Called by all 4 lanes of a row (lane = 4 r + s, the slice map above): chunk c
 // of lanes s = 2j, 2j + 1 is the 8-column group 2c + j, so the pair trades halves over one DPP
 // quad_perm [1,0,3,2] -- the even lane sends its lo parts and gets its partner's hi parts -- and
 // each lane stores one whole 16-B half (even: the group's hi parts, odd: its lo parts), the store
 // count of st16x. The lo parts are v_fma_mix, as gemm_kernel.h split_lo8 (their consumers here
 // are a VALU select and a store: no MFMA reads them, so no wait states in the statement).
-static_assert(CLIPK_F32_IL, "st16x_split: the interleaved slice map");
 __device__ __forceinline__ void st16x_split(float* __restrict__ p, const float* v, int s) {
   const bool odd = s & 1;
 #pragma unroll
@@ -270,16 +261,10 @@ __device__ __forceinline__ void store_tile64(T* rowp, const f32x4 (&o)[4], float
       d[s][dw] = r[0];
       d[s + 1][dw] = r[1];
     }
-  if (ok) {
+  if (ok) {  // plain stores (non-temporal ones measured slower when tried, commit d3ccf29; no profile kept)
     const int g4 = (threadIdx.x & 63) >> 4;
-#if CLIPK_ATTN_SNT  // build-time A/B knob: non-temporal output stores
-    __builtin_nontemporal_store((u32x4){d[0][0], d[0][1], d[1][0], d[1][1]}, reinterpret_cast<u32x4*>(rowp + 8 * g4));
-    __builtin_nontemporal_store((u32x4){d[2][0], d[2][1], d[3][0], d[3][1]},
-                                reinterpret_cast<u32x4*>(rowp + 32 + 8 * g4));
-#else
     *reinterpret_cast<u32x4*>(rowp + 8 * g4) = (u32x4){d[0][0], d[0][1], d[1][0], d[1][1]};
     *reinterpret_cast<u32x4*>(rowp + 32 + 8 * g4) = (u32x4){d[2][0], d[2][1], d[3][0], d[3][1]};
-#endif
   }
 }
 

@@ -420,18 +420,10 @@ static int block_attn(const clipk_encoder* e, const std::array<const void*, 16>&
 // Xo = Xm + MLP(xn). (The text encoder's last layer runs it on the EOT rows only.)
 // Residual stream X, Xm, Xo of dtype rd (fp32, or the 16-bit act dtype for the text encoder).
 // Training: c_fc writes both h (kept for the backward) and quickgelu(h) from its epilogue, and
-// c_proj stages quickgelu(h) like any operand, so it runs the ping-pong loop. Knob
-// CLIPK_TEXT_AQGELU=1: c_fc writes h alone and c_proj applies QuickGELU to A while staging it
-// (register-staged 2-slot loop). Same-box A/B (profiles/r02o_ab_aqgelu.txt): 12.33 -> 12.19 ms
-// per step with the epilogue form (c_proj 1.71 -> 1.22 ms, c_fc 1.19 -> 1.49 ms).
-static bool a_qgelu_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char* s = getenv("CLIPK_TEXT_AQGELU");
-    v = s ? atoi(s) : 0;
-  }
-  return v != 0;
-}
+// c_proj stages quickgelu(h) like any operand, so it runs the ping-pong loop. (c_fc writing h alone
+// and c_proj applying QuickGELU to A while staging it, the CLIPK_A_QGELU register-staged 2-slot
+// loop, measured slower: same-box A/B profiles/r02o_ab_aqgelu.txt, 12.33 -> 12.19 ms per step with
+// the epilogue form, c_proj 1.71 -> 1.22 ms, c_fc 1.19 -> 1.49 ms.)
 
 // PREC fp32s: the MLP's hand-offs in pre-split form (include/clipk.h CLIPK_OUT_SPLIT / CLIPK_A_SPLIT):
 // c_fc stores QuickGELU(h) as the fp16 parts c_proj's split would form, and the backward's dgelu
@@ -449,17 +441,6 @@ static bool presplit_on() {
 static int ps_out() { return t_split && presplit_on() ? CLIPK_OUT_SPLIT : 0; }
 static int ps_a() { return t_split && presplit_on() ? CLIPK_A_SPLIT : 0; }
 
-// Training's c_fc saves quickgelu'(h) for the backward (CLIPK_QGELU_DERIV) instead of h itself;
-// knob CLIPK_QGELU_DERIV=0 (A/B) saves h and the backward recomputes the derivative.
-static bool qgelu_deriv_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char* s = getenv("CLIPK_QGELU_DERIV");
-    v = s ? atoi(s) : 1;
-  }
-  return v != 0;
-}
-
 static int block_post(const clipk_encoder* e, const std::array<const void*, 16>& w, int rows, int rd,
                       const void* X, const void* o, void* Xm, void* Xo, void* xn, void* h, void* g, float* m2,
                       float* r2, hipStream_t st, bool text, void* sk, size_t skb) {
@@ -473,18 +454,10 @@ static int block_post(const clipk_encoder* e, const std::array<const void*, 16>&
     TRY(clipk_layernorm_fwd_x(rd, act, rows, W, Xm, W, nullptr, (const float*)w[6], (const float*)w[7], xn, W,
                               m2, r2, st));
   }
-  if (text && act != CLIPK_F32 && h && a_qgelu_on()) {
-    // knob: c_fc writes only the pre-activation h and c_proj applies QuickGELU to its A
-    // operand while staging it (no g write; measured slower than the ping-pong c_proj)
-    TRY(gemm(act, act, CLIPK_EPI_BIAS, rows, 4 * W, W, xn, w[8], (const float*)w[9], nullptr, h,
-             nullptr, nullptr, 0, st, CLIPK_PROF_GEMM_FC, nullptr, 0, "text.fc_fwd"));
-    TRY(gemm(act, rd, CLIPK_EPI_BIAS_RES | CLIPK_A_QGELU, rows, W, 4 * W, h, w[10], (const float*)w[11], Xm,
-             Xo, nullptr, nullptr, 0, st, pg, nullptr, 0, "text.proj_fwd"));
-    return CLIPK_OK;
-  }
   // training (h given): h receives quickgelu'(xn Wfc^T + b) for the backward (CLIPK_QGELU_DERIV)
+  // instead of the pre-activation itself
   const int pso = sk ? 0 : ps_out(), psa = sk ? 0 : ps_a();  // (split-K slices take no pre-split operands)
-  TRY(gemm(act, act, CLIPK_EPI_BIAS_QGELU | (h && qgelu_deriv_on() ? CLIPK_QGELU_DERIV : 0) | pso, rows, 4 * W, W, xn, w[8], (const float*)w[9],
+  TRY(gemm(act, act, CLIPK_EPI_BIAS_QGELU | (h ? CLIPK_QGELU_DERIV : 0) | pso, rows, 4 * W, W, xn, w[8], (const float*)w[9],
            nullptr, g, h, nullptr, 0, st, text ? CLIPK_PROF_GEMM_FC : CLIPK_PROF_NONE, sk, skb, text ? "text.fc_fwd" : "vit.fc_fwd"));
   TRY(gemm(act, rd, CLIPK_EPI_BIAS_RES | psa, rows, W, 4 * W, g, w[10], (const float*)w[11], Xm, Xo,
            nullptr, nullptr, 0, st, pg, sk, skb, text ? "text.proj_fwd" : "vit.proj_fwd"));
@@ -579,7 +552,7 @@ static int block_post_fold(const clipk_encoder* e, const std::array<const void*,
   else
     TRY(gemm_ln(act, CLIPK_EPI_BIAS_RES, rows, W, W, o, w[4], (const float*)w[5], X, Xm, nullptr, lnst, nullptr,
                 nullptr, st, pg, text ? "text.out_fwd" : "vit.out_fwd"));
-  TRY(gemm_ln_merged(act, CLIPK_EPI_BIAS_QGELU | (h && qgelu_deriv_on() ? CLIPK_QGELU_DERIV : 0) | ps_out() |
+  TRY(gemm_ln_merged(act, CLIPK_EPI_BIAS_QGELU | (h ? CLIPK_QGELU_DERIV : 0) | ps_out() |
                               (xs ? CLIPK_A_SPLIT : 0),
                      rows, 4 * W, W, xs ? xs : Xm, f[3], (const float*)f[5], g, h, lnst, (const float*)f[4], m2, r2,
                      rnb, st, text ? CLIPK_PROF_GEMM_FC : CLIPK_PROF_NONE, text ? "text.fc_fwd" : "vit.fc_fwd", text,
@@ -714,7 +687,7 @@ static bool ln_fold_on(const clipk_encoder* e, const EncIO& io) {
   // clipk_ln_stats_merge covers widths that are multiples of 128 up to 1024; wider encoders run
   // the LayerNorm passes
   return v != 0 && (int)e->fold.size() == e->layers && (e->act != CLIPK_F32 || e->split) && io.rd == e->act &&
-         e->W % 128 == 0 && e->W <= 1024 && !(e->deep.n_deep > 0 && e->deep.prompts) && !a_qgelu_on();
+         e->W % 128 == 0 && e->W <= 1024 && !(e->deep.n_deep > 0 && e->deep.prompts);
 }
 
 // deep prompts of layer l (1..n_deep) into the layer's input rows
@@ -998,11 +971,8 @@ static int text_backward_impl(const clipk_encoder* e, const SeqShape& sh, const 
     return clipk_layernorm_bwd_x2(rd, gd, n, W, b.dxn, W, x, W, nullptr, gamma, mean, rstd, b.dX_lp, gd, W,
                                   last ? dX : nullptr, b.dX_lp, gd, nullptr, W, st);
   };
-  // the forward saved quickgelu'(h) in t.h (CLIPK_QGELU_DERIV), except on the A-operand QuickGELU
-  // knob's path (block_post), whose c_proj reads the pre-activation h itself
-  const int dgelu_epi = (io.text && act != CLIPK_F32 && a_qgelu_on()) || !qgelu_deriv_on()
-                            ? CLIPK_EPI_DQGELU
-                            : (CLIPK_EPI_DQGELU | CLIPK_QGELU_DERIV);
+  // the forward saved quickgelu'(h) in t.h (CLIPK_QGELU_DERIV)
+  const int dgelu_epi = CLIPK_EPI_DQGELU | CLIPK_QGELU_DERIV;
   for (int l = e->layers - 1; l >= 0; --l) {
     const auto& w = e->lw[l];
     if (!w[12] || !w[13] || !w[14] || !w[15]) return CLIPK_EINVAL;
@@ -1012,12 +982,11 @@ static int text_backward_impl(const clipk_encoder* e, const SeqShape& sh, const 
     // in the act dtype (16-bit: rms 1.8e-4 on the derivative vs 2.9e-5 when recomputing it from a
     // 16-bit h -- under the 16-bit rounding of dh itself -- for no exp / rcp in this epilogue)
     // (the last layer's compact EOT-row launches are sites of their own: a different GEMM grid)
-    // (PREC fp32s: dh handed to fc_dx pre-split, presplit_on; the saved-derivative form only)
-    const bool dh_split = (dgelu_epi & CLIPK_QGELU_DERIV) != 0;
-    TRY(gemm(gd, gd, dgelu_epi | (dh_split ? ps_out() | dA_split : 0), n, 4 * W, W, dA, w[15], nullptr, nullptr,
+    // (PREC fp32s: dh handed to fc_dx pre-split, presplit_on)
+    TRY(gemm(gd, gd, dgelu_epi | ps_out() | dA_split, n, 4 * W, W, dA, w[15], nullptr, nullptr,
              b.dh, nullptr, t.h[l], act, st, io.text ? CLIPK_PROF_GEMM_DGELU : CLIPK_PROF_NONE, nullptr, 0,
              compact ? SITE("proj_dx_dgelu_eot") : SITE("proj_dx_dgelu")));
-    TRY(gemm(gd, gd, CLIPK_EPI_NONE | (dh_split ? ps_a() : 0), n, W, 4 * W, b.dh, w[14], nullptr, nullptr, b.dxn,
+    TRY(gemm(gd, gd, CLIPK_EPI_NONE | ps_a(), n, W, 4 * W, b.dh, w[14], nullptr, nullptr, b.dxn,
              nullptr, nullptr, 0, st, pg, nullptr, 0, compact ? SITE("fc_dx_eot") : SITE("fc_dx")));
     TRY(ln_bwd(n, t.Xm[l], (const float*)w[6], t.mean2[l], t.rstd2[l], false));
     // attention: do = dXm . Wout ; dqkv ; dxn1 = dqkv . Win

@@ -140,7 +140,6 @@ int num_cus() {
 int pp_grid(int nwg, int cus) {
   const int full = (cus / 8) * 8;
   const int need = (nwg + 7) / 8 * 8;
-  if (CLIPK_GEMM_PP == 2) return need;  // one tile per block (A/B)
   return need < full ? need : full;
 }
 
@@ -153,11 +152,7 @@ template <typename T, typename TO, typename TX, int EPI, int LNM = 0>
 static int launch_gemm(const GemmArgs& g, hipStream_t st) {
   const int cfg = pick_cfg(g.M, g.N, (int)sizeof(T));
   const_cast<GemmArgs&>(g).stamp = gemm_stamp_buf();
-  if (g_skew < 0) {
-    const char* e = getenv("CLIPK_GEMM_SKEW");
-    g_skew = e ? atoi(e) : 0;
-  }
-  const_cast<GemmArgs&>(g).skew = g_skew;
+  const_cast<GemmArgs&>(g).skew = gemm_skew();
   if constexpr (__is_same(T, float)) {
     const int nwg = ((g.M + 127) / 128) * (g.N / 128);
     hipLaunchKernelGGL((gemm_nt_kernel<T, TO, TX, EPI, 128, 128, 2, 2, false, GEMM_ROWB, 2, false, false, LNM>), dim3(nwg), dim3(256), 0, st, g);
@@ -177,9 +172,7 @@ static int launch_gemm(const GemmArgs& g, hipStream_t st) {
       const int nwg = ((g.M + 191) / 192) * (g.N / 256);
       const int cus = num_cus();
       if (try_pp<T, TO, TX, EPI, 192, LNM>(g, nwg, st)) {
-      } else if constexpr (CLIPK_GEMM_RING)  // 4-slot ring of 64-B K steps: three steps in flight
-        hipLaunchKernelGGL((gemm_nt_kernel<T, TO, TX, EPI, 192, 256, 2, 4, false, 64, 4, false, false, LNM>), dim3(nwg), dim3(512), 0, st, g);
-      else if (nwg > persist_min(cus))
+      } else if (nwg > persist_min(cus))
         hipLaunchKernelGGL((gemm_nt_kernel<T, TO, TX, EPI, 192, 256, 2, 4, true, GEMM_ROWB, 2, false, false, LNM>), dim3((cus / 8) * 8), dim3(512), 0, st, g);
       else
         hipLaunchKernelGGL((gemm_nt_kernel<T, TO, TX, EPI, 192, 256, 2, 4, false, GEMM_ROWB, 2, false, false, LNM>), dim3(nwg), dim3(512), 0, st, g);
@@ -587,17 +580,13 @@ static bool ln_merge_fused_ok(int in_dtype, int M, int N, int K) {
     const char* e = getenv("CLIPK_LN_MERGE_FUSED");
     on = e ? atoi(e) : 1;
   }
-  return on && CLIPK_GEMM_PP && (in_dtype == CLIPK_F16 || in_dtype == CLIPK_BF16) && K == 512 && N % 256 == 0 &&
+  return on && (in_dtype == CLIPK_F16 || in_dtype == CLIPK_BF16) && K == 512 && N % 256 == 0 &&
          pick_cfg(M, N, 2) == 6;
 }
 template <typename T, int EPI>
 static int launch_ln_merge(GemmArgs g, hipStream_t st) {
   g.stamp = gemm_stamp_buf();
-  if (g_skew < 0) {
-    const char* e = getenv("CLIPK_GEMM_SKEW");
-    g_skew = e ? atoi(e) : 0;
-  }
-  g.skew = g_skew;
+  g.skew = gemm_skew();
   const int nwg = ((g.M + 191) / 192) * (g.N / 256);
   hipLaunchKernelGGL((gemm_nt_kernel<T, T, float, EPI, 192, 256, 2, 4, true, GEMM_ROWB, 2, false, true, 3>),
                      dim3(pp_grid(nwg, num_cus())), dim3(512), 0, st, g);

@@ -29,15 +29,6 @@
 
 namespace clipk {
 
-// residual / aux lookahead ring of the 256-row tiles, VGPRs: 16 = two row groups of a 16-bit
-// aux (the dgelu GEMM's h) in flight; still no spill at 251 VGPRs. Same-box A/B
-// (profiles/r02r/ab_xbud256.txt): dgelu 1.587 -> 1.488 ms/step, headline 11.92 -> 11.80 ms.
-#ifndef CLIPK_XBUD256
-#define CLIPK_XBUD256 16
-#endif
-#ifndef CLIPK_XBUD192
-#define CLIPK_XBUD192 32
-#endif
 constexpr int GEMM_ROWB = 128;  // bytes per staged row (BK = 64 halfs / 32 floats)
 constexpr int GEMM_NMIN = 128;  // N granularity accepted by the C-ABI
 constexpr int EPI_SCRATCH = 16 * 64 * 4;  // per-wave epilogue transpose tile [16][64] fp32
@@ -125,9 +116,6 @@ __device__ __forceinline__ f32x4 mma(u32x4 a, u32x4 b, f32x4 c) {
 // With `s_nop 1` inside the string the parts are safe for any consumer hipcc schedules after
 // the statement, so no caller counts wait states (round 5 counted them by hand: an MFMA two
 // instructions after the split read stale parts, off by up to 5.8e-2, profiles/r05w16/hazard.txt).
-#ifndef CLIPK_SPLIT_MIX
-#define CLIPK_SPLIT_MIX 1
-#endif
 __device__ __forceinline__ void split_lo8(const f32x4& x0, const f32x4& x1, const u32x4& hi, u32x4& lo) {
   unsigned l0, l1, l2, l3;
   asm("v_fma_mixlo_f16 %0, %4, 1.0, -%12 op_sel_hi:[0,0,1]\n\t"
@@ -144,8 +132,6 @@ __device__ __forceinline__ void split_lo8(const f32x4& x0, const f32x4& x1, cons
         "v"(hi[0]), "v"(hi[1]), "v"(hi[2]), "v"(hi[3]));
   lo = (u32x4){l0, l1, l2, l3};
 }
-// MIX false: the lo part in compiler-visible cvt + sub + cvt form (A/B knob CLIPK_SPLIT_MIX=0).
-template <bool MIX = CLIPK_SPLIT_MIX != 0>
 __device__ __forceinline__ void split8(u32x4 a0, u32x4 a1, u32x4& hi, u32x4& lo) {
   // the inputs as materialised fp32 values: a caller's x * gamma (the fold's LayerNorm weight) must
   // not contract with the x - hi below into one fma (the parts of the unrounded product), so every
@@ -159,47 +145,25 @@ __device__ __forceinline__ void split8(u32x4 a0, u32x4 a1, u32x4& hi, u32x4& lo)
     h[4 + c] = (f16)x1[c];
   }
   hi = __builtin_bit_cast(u32x4, h);
-  if constexpr (!MIX) {
-    f16x8 l;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      l[c] = (f16)(x0[c] - (float)h[c]);
-      l[4 + c] = (f16)(x1[c] - (float)h[4 + c]);
-    }
-    lo = __builtin_bit_cast(u32x4, l);
-    return;
-  }
   split_lo8(x0, x1, hi, lo);
 }
 // a . b ~= hi(a) hi(b) + hi(a) lo(b) + lo(a) hi(b) (lo . lo ~ 2^-22 relative is dropped); the
 // weight's parts (packed, clipk_split_pack) are the instruction's A operand (swapped operands)
-// Precision experiment (build-time, A/B only): CLIPK_SPLIT_TERMS 2 drops the
-// lo(a) hi(b) term -- the activation operand rounded to fp16, the weight kept at ~22 bits -- in
-// the GEMMs of epilogue class `CLIPK_SPLIT_TERMS_EPI` (0: every GEMM, 1: the backward's input-grad
-// GEMMs, EPI_NONE / EPI_DMUL / EPI_DQGELU).
-#ifndef CLIPK_SPLIT_TERMS
-#define CLIPK_SPLIT_TERMS 3
-#endif
-#ifndef CLIPK_SPLIT_TERMS_EPI
-#define CLIPK_SPLIT_TERMS_EPI 0
-#endif
+// (Dropping the lo(a) hi(b) term -- the activation rounded to fp16 -- was a precision experiment,
+// not shipped.)
 // W16 (CLIPK_F32S16): lo(b) is zero, so the hi(a) lo(b) product adds exact zeros and is skipped
 // (the compiler then drops the lo(b) fragment reads from LDS too)
-template <bool TWO = false, bool W16 = false>
+template <bool W16 = false>
 __device__ __forceinline__ f32x4 mma_split(u32x4 bh, u32x4 bl, u32x4 ah, u32x4 al, f32x4 c) {
   if constexpr (!W16)
     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, bl), __builtin_bit_cast(f16x8, ah), c, 0, 0, 0);
-  if constexpr (!TWO)
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, bh), __builtin_bit_cast(f16x8, al), c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, bh), __builtin_bit_cast(f16x8, al), c, 0, 0, 0);
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, bh), __builtin_bit_cast(f16x8, ah), c, 0,
                                                 0, 0);
 }
 // Split-form epilogue stores form the lo parts by v_fma_mix, and the LayerNorm fold carries the
-// weights' scale on the row's rstd (A/B knob: 0 = the convert / subtract form and a multiply per
-// element; bitwise the same outputs)
-#ifndef CLIPK_EPI_MIXSPLIT
-#define CLIPK_EPI_MIXSPLIT 1
-#endif
+// weights' scale on the row's rstd (the convert / subtract form with a multiply per element gave
+// bitwise the same outputs; same-box A/B profiles/r06n/ab.txt)
 constexpr float kSplitAlpha = 1.0f / CLIPK_SPLIT_SCALE;  // the packed weights' scale, undone
 
 // Training's QuickGELU pair with the derivative saved (CLIPK_QGELU_DERIV, include/clipk.h):
@@ -221,104 +185,25 @@ template <> struct Raw<8> { uint2 v; };
 template <> struct Raw<16> { uint4 v; };
 template <> struct Raw<32> { uint4 v[2]; };
 
-// Cache policy of the epilogue's streaming traffic (build-time A/B knobs, tools/ab_bench.sh):
-// CLIPK_GEMM_SPOL = the output stores' cache-policy bits, CLIPK_GEMM_XNT = non-temporal
-// residual / aux loads. Headline step (profiles/r02k_ab_cache_policy.txt): plain 12.70 ms;
-// nt stores (2) 12.43 -- every GEMM 4-9 % faster, their consumers (LayerNorm, attention) a
-// little slower; sc1 stores (16, the line leaves the XCD's L2) 12.72; nt stores + nt aux /
-// residual loads 12.37-12.43 (dgelu 1.61 -> 1.55 ms/step): the default.
-#ifndef CLIPK_GEMM_SPOL
-#define CLIPK_GEMM_SPOL 2
-#endif
-#ifndef CLIPK_GEMM_XNT
-#define CLIPK_GEMM_XNT 1
-#endif
+// Cache policy of the epilogue's streaming traffic. Headline step
+// (profiles/r02k_ab_cache_policy.txt): plain 12.70 ms; nt stores (2) 12.43 -- every GEMM 4-9 %
+// faster, their consumers (LayerNorm, attention) a little slower; sc1 stores (16, the line leaves
+// the XCD's L2) 12.72; nt stores + nt aux / residual loads (ld_raw) 12.37-12.43 (dgelu 1.61 ->
+// 1.55 ms/step): shipped.
+constexpr int kStorePol = 2;
 // Store policy of a residual stream written with LN statistics (clipk_gemm_ln producers): its
 // consumer is the next GEMM's A operand, re-read by every column tile, so the lines are kept
 // (plain stores) rather than streamed past the caches. Same-box A/B of the fold
 // (profiles/r03c/ab_lnfold.txt): with nt stores the folded c_fc ran 0.24 ms/step slower than
 // the LayerNorm-pass c_fc; with plain stores 0.04 ms.
-#ifndef CLIPK_GEMM_SPOL_LN
-#define CLIPK_GEMM_SPOL_LN 0
-#endif
+constexpr int kStorePolLn = 0;
 // Store policy of the outputs the NEXT GEMM reads as its A operand: c_fc's QuickGELU(h) (c_proj,
 // forward) and dgelu's dh (fc_dx, backward). c_fc's second output (the saved QuickGELU', read a
-// whole forward + backward later) keeps CLIPK_GEMM_SPOL.
-#ifndef CLIPK_GEMM_SPOL_CHAIN
-#define CLIPK_GEMM_SPOL_CHAIN 2
-#endif
-// CLIPK_GEMM_PP: 192x256 / 256x256 launches with >= 2 K tiles run the ping-pong main loop
-// (1, persistent; 2 = one tile per block, A/B; 0 = the 2-slot loop). Same-box A/B
-// (profiles/r02m_ab_pingpong.txt): headline step 12.60 -> 12.13 ms, input-grad GEMMs
-// 2.65 -> 2.27 ms/step; staging by global_load_lds with per-lane 64-bit addresses instead of
-// buffer LDS-DMA measured 12.80 ms (the address arithmetic sits in the memory segments).
-#ifndef CLIPK_GEMM_PP
-#define CLIPK_GEMM_PP 1
-#endif
-// CLIPK_GEMM_RING (A/B): 192x256 launches as non-persistent 4-slot rings of 64-B K steps.
-#ifndef CLIPK_GEMM_RING
-#define CLIPK_GEMM_RING 0
-#endif
-// CLIPK_GEMM_PPB0: the ping-pong loop keeps phase 1's B-half-0 fragments in registers for
-// phase 4 instead of re-reading them (4 of 24 ds_read_b128 per wave and K tile, +13-16 VGPRs,
-// no spill at 256 rows). Same-box A/B (profiles/r02o_ab_ppb0.txt): headline step 11.91 ->
-// 11.82 ms, input-grad GEMMs 2.195 -> 2.166 ms/step.
-#ifndef CLIPK_GEMM_PPB0
-#define CLIPK_GEMM_PPB0 1
-#endif
-// CLIPK_GEMM_PP2: the ping-pong loop in 2 phases per K tile instead of 4 -- (A half 0 x all of
-// B), (A half 1 x all of B), B's fragments read once and kept in registers -- so each wave
-// crosses 4 barriers per K tile instead of 8 and each MFMA segment is 24 MFMAs instead of 12.
-// Restage: A1 + B1 of K tile t+1 in phase 1, A0 + B0 of t+2 in phase 2 (each one phase after
-// its last read by the lagging wave row); phase 2's counted vmcnt leaves only those in flight.
-// 1 = every ping-pong tile, 2 = the 256-row tiles only (default), 0 = off. Same-box A/Bs
-// (profiles/r03i/ab_pp2.txt): on the 256-row tiles (qkv / c_fc forward, dgelu) 1-3 % faster per
-// launch, headline 10.70 -> 10.57 ms/step; on the 192-row tiles (the N = 512 GEMMs) 1-2 % slower.
-// PMC over both shapes: no LDS bank conflicts or unaligned replays, the LDS array busy ~25 % and
-// the MFMA pipes ~45 % of the kernel's cycles -- the loop is bound by its issue / synchronisation
-// structure rather than by either unit.
-#ifndef CLIPK_GEMM_PP2
-#define CLIPK_GEMM_PP2 2
-#endif
-// CLIPK_GEMM_PRIO (A/B): wave priority in the ping-pong loop -- 1 = the MFMA segment runs at
-// priority 1 (default), 0 = no priority changes, 2 = the memory segment (fragment reads,
-// restage issue) runs at priority 1 instead.
-#ifndef CLIPK_GEMM_PRIO
-#define CLIPK_GEMM_PRIO 1
-#endif
-// CLIPK_GEMM_APOL (A/B, build-time): cache-policy bits of the ping-pong loop's A-operand LDS-DMA
-// (0 default; the staging lab read 100 -> 96.5 us with sc0 (1) or sc1 (16), profiles/r05zh/)
-#ifndef CLIPK_GEMM_APOL
-#define CLIPK_GEMM_APOL 0
-#endif
-// CLIPK_GEMM_WARM (A/B, build-time; 0 = off): the 192-row ping-pong loop (16-bit) touches one
-// dword of every 128-B line of the A panel CLIPK_GEMM_WARM K steps ahead (waves 0-2, one line per
-// lane), so the first read of each activation line is in flight before its LDS-DMA. The staging
-// lab measured 100 -> 94 us for this tile's operand stream at 2 steps ahead
-// (tools/lab/stage_lab.hip, profiles/r05zh/).
-#ifndef CLIPK_GEMM_WARM
-#define CLIPK_GEMM_WARM 0
-#endif
-// Diagnostic builds only (wrong results; tools/gemm_diag.sh): NOLOAD = stage no K step past
-// the first (the loop's compute + LDS + barrier ceiling), NOBAR = no barrier / vmcnt wait per
-// K step either.
-#ifndef CLIPK_GEMM_NOLOAD
-#define CLIPK_GEMM_NOLOAD 0
-#endif
-#ifndef CLIPK_GEMM_NOBAR
-#define CLIPK_GEMM_NOBAR 0
-#endif
-// NOMMA = no MFMA in the ping-pong loop (its load + LDS + barrier time alone).
-#ifndef CLIPK_GEMM_NOMMA
-#define CLIPK_GEMM_NOMMA 0
-#endif
-// NOSPLIT = the split GEMMs' ping-pong loop takes A's fp32 bits as its hi / lo parts (no split VALU:
-// the loop's ceiling without the activation split).
-#ifndef CLIPK_GEMM_NOSPLIT
-#define CLIPK_GEMM_NOSPLIT 0
-#endif
+// whole forward + backward later) keeps kStorePol. Plain / sc1 stores for these measured slower,
+// 10.55-10.61 -> 10.80-10.87 ms/step (profiles/r05_lab/ab_store_policy.txt).
+constexpr int kStorePolChain = 2;
+// residual / aux operand run, non-temporal (see kStorePol)
 template <int NB> __device__ __forceinline__ void ld_raw(const void* p, Raw<NB>& r) {
-#if CLIPK_GEMM_XNT
   typedef unsigned int nt2 __attribute__((ext_vector_type(2)));
   typedef unsigned int nt4 __attribute__((ext_vector_type(4)));
   if constexpr (NB == 8) {
@@ -329,11 +214,6 @@ template <int NB> __device__ __forceinline__ void ld_raw(const void* p, Raw<NB>&
     r.v[0] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const nt4*>(p)));
     r.v[1] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const nt4*>(p) + 1));
   }
-#else
-  if constexpr (NB == 8) r.v = *reinterpret_cast<const uint2*>(p);
-  else if constexpr (NB == 16) r.v = *reinterpret_cast<const uint4*>(p);
-  else { r.v[0] = reinterpret_cast<const uint4*>(p)[0]; r.v[1] = reinterpret_cast<const uint4*>(p)[1]; }
-#endif
 }
 template <typename TX, int CW, int NB>
 __device__ __forceinline__ void raw_f32(const Raw<NB>& r, float* o) {
@@ -358,7 +238,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const void* base, lo
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)n, 0x00020000);
 }
 // 16 bytes of TO (16 / sizeof(TO) fp32 values converted) at byte offset off
-template <typename TO, int POL = CLIPK_GEMM_SPOL>
+template <typename TO, int POL = kStorePol>
 __device__ __forceinline__ void buf_store16(__amdgpu_buffer_rsrc_t r, int off, const float* v) {
   u32x4 d;
   if constexpr (sizeof(TO) == 4) {
@@ -436,9 +316,6 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
   constexpr bool GAMMA_A = LN_GAMMA && !A_PRE;  // gamma applied to A's fragments here
   static_assert(!SPF || SPLIT, "pre-split operands: split GEMMs only");
   static_assert(!O_SPLIT || (sizeof(TO) == 4 && EPI != CLIPK_EPI_BIAS_RES), "split-form output: not the residual stream");
-  [[maybe_unused]] constexpr bool TWO_TERMS =
-      CLIPK_SPLIT_TERMS == 2 && (CLIPK_SPLIT_TERMS_EPI == 0 || EPI == CLIPK_EPI_NONE || EPI == CLIPK_EPI_DQGELU ||
-                                 EPI == EPI_DMUL);
   static_assert(!SPLIT || (ROWB == 128 && !AG), "split-fp16 GEMM: 128-B staged rows");
   static_assert(!PP || (PERSIST && !AG && DEPTH == 2 && ROWB == 128 && WM == 2 && WN == 4 && BN == 256 &&
                         (sizeof(T) == 2 || SPLIT) && BM % 64 == 0), "ping-pong main loop (K >= 128)");
@@ -467,9 +344,7 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
   static_assert(ROWB == 128 || (ROWB == 64 && sizeof(T) == 2), "staged row is 128 B (or 64 B for 16-bit)");
   static_assert(BM % RPI == 0 && BN % RPIB == 0 && NG >= NW, "tile/wave mismatch");
   static_assert(!AG || BLOCKED, "A-operand QuickGELU path: blocked unit split");
-  // (+ 1 KiB: the CLIPK_GEMM_WARM junk area of the 192-row ping-pong loop)
-  constexpr int WARM_B = CLIPK_GEMM_WARM > 0 && PP && BM == 192 ? 1024 : 0;
-  constexpr int GAM_OFF = DEPTH * STAGE + NW * EPI_SCRATCH + WARM_B;  // LNM 4: gamma[K] in LDS
+  constexpr int GAM_OFF = DEPTH * STAGE + NW * EPI_SCRATCH;  // LNM 4: gamma[K] in LDS
   __shared__ CLIPK_LDS_ALIGN char smem[GAM_OFF + (GAMMA_A ? kGammaMax * 4 : 0)];  // one array (see header)
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -529,7 +404,6 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
   };
   u32x4 ra[AG ? IA : 1];  // AG: the next stage's A chunks in flight
   auto stage = [&](int s, int kt) {
-    if (CLIPK_GEMM_NOLOAD && kt > 0) return;
     char* base = smem + s * STAGE;
     const size_t koff = (size_t)kt * ROWB, koffb = (size_t)kt * ROWBB;
 #pragma unroll
@@ -633,8 +507,12 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
     constexpr int XNB = CW * (int)sizeof(TX);
     typedef Raw<XNB> XR;
     constexpr int XREG = NQ * XNB / 4;
-    // ring VGPRs (256-row tiles: little to spare; the LN-statistics epilogue needs 8 more)
-    constexpr int XBUD = BM == 192 ? CLIPK_XBUD192 : (LNM == 1 ? CLIPK_XBUD256 / 2 : CLIPK_XBUD256);
+    // ring VGPRs. 256-row tiles (little to spare; the LN-statistics epilogue needs 8 more): 16 = two
+    // row groups of a 16-bit aux (the dgelu GEMM's h) in flight, still no spill at 251 VGPRs; same-box
+    // A/B (profiles/r02r/ab_xbud256.txt) dgelu 1.587 -> 1.488 ms/step, headline 11.92 -> 11.80 ms.
+    // 192-row tiles: 32 vs 48 VGPRs 11.97 vs 11.94 ms, within noise (profiles/r02s/ab_xbud192.txt)
+    constexpr int kXbud256 = 16, kXbud192 = 32;
+    constexpr int XBUD = BM == 192 ? kXbud192 : (LNM == 1 ? kXbud256 / 2 : kXbud256);
     constexpr int XD = XBUD / XREG < 1 ? 1 : (XBUD / XREG > TM ? TM : XBUD / XREG);
     XR extq[XD][NQ];
     auto load_ext = [&](int i, XR* dst) {
@@ -726,46 +604,32 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
       // stage region r of K tile kt into buffer buf from the tile resources ra / rb
       // kt: absolute K tile (the item's kt0c + local index; the next item's kt0n + ...)
       auto pst = [&](int buf, __amdgpu_buffer_rsrc_t ra_, __amdgpu_buffer_rsrc_t rb_, int kt, int r) {
-        if (CLIPK_GEMM_NOLOAD && it >= 1) return;  // diagnostic: first K tiles only
         const int base = buf * STAGE;
         const int koff = kt * (r < 2 ? ROWB : ROWBB);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
           if ((r >= 2 && i < NBR) || (r < 2 && (i == 0 || two_a))) {
             const int row0 = unit_row0(r, i);
-            if (CLIPK_GEMM_APOL != 0 && r < 2)
-              __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                  ra_, (__attribute__((address_space(3))) void*)(smem + base + row0 * ROWB), 16, poff[r][i], koff, 0,
-                  CLIPK_GEMM_APOL);
-            else
-              __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                  r < 2 ? ra_ : rb_,
-                  (__attribute__((address_space(3))) void*)(smem + base + (r < 2 ? row0 * ROWB : OPA + row0 * ROWBB)),
-                  16, poff[r][i], koff, 0, 0);
+            // (an sc0 / sc1 cache policy on A's LDS-DMA measured null, profiles/r05zh/ab_apol.txt)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                r < 2 ? ra_ : rb_,
+                (__attribute__((address_space(3))) void*)(smem + base + (r < 2 ? row0 * ROWB : OPA + row0 * ROWBB)),
+                16, poff[r][i], koff, 0, 0);
           }
       };
-      // K step s+1 landed; the three regions already issued for s+2 (A0, B1, A1) stay in flight
-      // (+ the warm-up load issued between B1 and A1, CLIPK_GEMM_WARM): this wave's LDS-DMAs of
-      // those regions, 2 or 1 per A region (two_a) and NBR per B region
-      constexpr bool WARM = CLIPK_GEMM_WARM > 0 && BM == 192 && !SPLIT;
-      const bool warm_w = WARM && w < BM / 64;
+      // K step s+1 landed; the three regions already issued for s+2 (A0, B1, A1) stay in flight:
+      // this wave's LDS-DMAs of those regions, 2 or 1 per A region (two_a) and NBR per B region.
+      // (Touching the A panel's lines 2-3 K steps ahead to warm L2 measured slower on the step,
+      // 10.55 -> 10.84-10.96 ms, profiles/r05zh/ab_warm.txt.)
       auto wait_ahead = [&]() {
-        if (warm_w) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(5 + NBR) : "memory");
-        else if (two_a) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + NBR) : "memory");
+        if (two_a) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + NBR) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 + NBR) : "memory");
       };
-      // one dword of A row (w * 64 + lane) of the tile at K tile kw: its 128-B line into L2, by an
-      // LDS-DMA into a junk area (no register result, so no compiler wait; wait_ahead counts it)
-      auto warm = [&](__amdgpu_buffer_rsrc_t ra_, int kw) {
-        if constexpr (WARM) {
-          if (warm_w)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                ra_, (__attribute__((address_space(3))) void*)(smem + DEPTH * STAGE + NW * EPI_SCRATCH + w * 256), 4,
-                (w * 64 + lane) * g.lda * (int)esz, kw * ROWB, 0, 0);
-        }
-      };
-      constexpr int NFB = CLIPK_GEMM_PPB0 ? 2 : 1;
-      u32x4 fa[KK][TM2], fbs[NFB][KK][TN2];
+      // both B halves' fragments stay in registers: phase 4 reuses phase 1's B half 0 instead of
+      // re-reading it (4 of 24 ds_read_b128 per wave and K tile, +13-16 VGPRs, no spill at 256
+      // rows). Same-box A/B (profiles/r02o_ab_ppb0.txt): headline step 11.91 -> 11.82 ms,
+      // input-grad GEMMs 2.195 -> 2.166 ms/step.
+      u32x4 fa[KK][TM2], fbs[2][KK][TN2];
       int kga = 0;  // LNM 4: the absolute K step whose A fragments rd_a reads
       [[maybe_unused]] f32x4 gam[2];
       auto rd_a = [&](int buf, int h) {
@@ -785,9 +649,9 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
         if constexpr (B16) {  // the hi parts only: chunk fq of the 64-B row (slot 1 unused)
 #pragma unroll
           for (int j = 0; j < TN2; ++j) {
-            fbs[NFB == 2 ? q : 0][0][j] =
+            fbs[q][0][j] =
                 *reinterpret_cast<const u32x4*>(Bs + j * 16 * ROWBB + ((fq ^ swz_rb(fr, ROWBB)) * 16));
-            fbs[NFB == 2 ? q : 0][1][j] = fbs[NFB == 2 ? q : 0][0][j];
+            fbs[q][1][j] = fbs[q][0][j];
           }
           return;
         }
@@ -795,18 +659,19 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
         for (int kk = 0; kk < KK; ++kk)
 #pragma unroll
           for (int j = 0; j < TN2; ++j)
-            fbs[NFB == 2 ? q : 0][kk][j] =
+            fbs[q][kk][j] =
                 *reinterpret_cast<const u32x4*>(Bs + j * 16 * ROWB + (((SPLIT ? 2 * fq + kk : kk * 4 + fq)) ^ sw) * 16);
       };
       auto mm = [&](int h, int q) {
-        if (CLIPK_GEMM_NOMMA) return;
-        if (CLIPK_GEMM_PRIO == 1) __builtin_amdgcn_s_setprio(1);
+        // the MFMA segment runs at wave priority 1 (no priority changes, or the memory segment
+        // raised instead: profiles/r03m/ab_prio.txt)
+        __builtin_amdgcn_s_setprio(1);
         if constexpr (SPLIT) {  // fa[0][i] / fa[1][i]: the A half's hi / lo parts (split_a)
 #pragma unroll
           for (int i = 0; i < TM2; ++i)
 #pragma unroll
             for (int j = 0; j < TN2; ++j)
-              acc[h * TM2 + i][q * TN2 + j] = mma_split<TWO_TERMS, W16>(fbs[NFB == 2 ? q : 0][0][j], fbs[NFB == 2 ? q : 0][1][j],
+              acc[h * TM2 + i][q * TN2 + j] = mma_split<W16>(fbs[q][0][j], fbs[q][1][j],
                                                         fa[0][i], fa[1][i], acc[h * TM2 + i][q * TN2 + j]);
         } else {
 #pragma unroll
@@ -815,9 +680,9 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
           for (int i = 0; i < TM2; ++i)
 #pragma unroll
             for (int j = 0; j < TN2; ++j)
-              acc[h * TM2 + i][q * TN2 + j] = mma<T>(fbs[NFB == 2 ? q : 0][kk][j], fa[kk][i], acc[h * TM2 + i][q * TN2 + j]);
+              acc[h * TM2 + i][q * TN2 + j] = mma<T>(fbs[q][kk][j], fa[kk][i], acc[h * TM2 + i][q * TN2 + j]);
         }
-        if (CLIPK_GEMM_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
       };
       // PREC fp32s: an A half just read is split into its hi / lo parts in place, once for both
       // B quadrants it meets, in the memory segment (beside the partner wave's MFMAs)
@@ -829,14 +694,13 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
               fa[0][i] = __builtin_bit_cast(u32x4, __builtin_bit_cast(f32x4, fa[0][i]) * gam[0]);
               fa[1][i] = __builtin_bit_cast(u32x4, __builtin_bit_cast(f32x4, fa[1][i]) * gam[1]);
             }
-            if constexpr (!CLIPK_GEMM_NOSPLIT) split8(fa[0][i], fa[1][i], fa[0][i], fa[1][i]);
+            split8(fa[0][i], fa[1][i], fa[0][i], fa[1][i]);
           }
         }
       };
       auto seg_end = [&](bool new_a = false) {  // memory segment done: fragments in registers, then the barrier
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (new_a) split_a();
-        if (CLIPK_GEMM_PRIO == 2) __builtin_amdgcn_s_setprio(0);
         G8_BAR();
       };
       // The K steps of this block's tiles form one stream (step `it`, buffer it & 1): the
@@ -859,8 +723,17 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
         if (two_a) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 + NBR) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(1 + NBR) : "memory");
       };
-      constexpr bool PP2 = CLIPK_GEMM_PP2 == 1 || (CLIPK_GEMM_PP2 == 2 && BM == 256);
-      static_assert(!PP2 || NFB == 2, "PP2 keeps all of B's fragments");
+      // PP2: the ping-pong loop in 2 phases per K tile instead of 4 -- (A half 0 x all of B), (A half 1
+      // x all of B) -- so each wave crosses 4 barriers per K tile instead of 8 and each MFMA segment
+      // is 24 MFMAs instead of 12. Restage: A1 + B1 of K tile t+1 in phase 1, A0 + B0 of t+2 in
+      // phase 2 (each one phase after its last read by the lagging wave row); phase 2's counted
+      // vmcnt leaves only those in flight. On the 256-row tiles only: same-box A/Bs
+      // (profiles/r03i/ab_pp2.txt) there (qkv / c_fc forward, dgelu) 1-3 % faster per launch,
+      // headline 10.70 -> 10.57 ms/step; on the 192-row tiles (the N = 512 GEMMs) 1-2 % slower.
+      // PMC over both shapes: no LDS bank conflicts or unaligned replays, the LDS array busy ~25 %
+      // and the MFMA pipes ~45 % of the kernel's cycles -- the loop is bound by its issue /
+      // synchronisation structure rather than by either unit.
+      constexpr bool PP2 = BM == 256;
       if (it == 0) {
         const int q0 = kt0c, q1 = kt0c + 1;
         if constexpr (PP2) {
@@ -886,7 +759,6 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
         const int k1 = in1 ? kt0c + kt + 1 : kt0n + kt + 1 - nkc, k2 = in2 ? kt0c + kt + 2 : kt0n + kt + 2 - nkc;
         const TRes ra1 = in1 ? cra : xra, rb1 = in1 ? crb : xrb;
         const TRes ra2 = in2 ? cra : xra, rb2 = in2 ? crb : xrb;
-        if (CLIPK_GEMM_PRIO == 2) __builtin_amdgcn_s_setprio(1);
         rd_a(b, 0); rd_b(b, 0); rd_b(b, 1);     // phase 1: A0 x B
         if (h1) {
           pst(b ^ 1, ra1, rb1, k1, 1);
@@ -900,7 +772,6 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
         mm(0, 0);
         mm(0, 1);
         G8_BAR();
-        if (CLIPK_GEMM_PRIO == 2) __builtin_amdgcn_s_setprio(1);
         rd_a(b, 1);                             // phase 2: A1 x B
         if (h2) {
           pst(b, ra2, rb2, k2, 0);
@@ -921,7 +792,6 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
         const bool in1 = kt + 1 < nkc, in2 = kt + 2 < nkc;
         const bool h1 = in1 || has_next, h2 = in2 || has_next;
         const int k1 = in1 ? kt0c + kt + 1 : kt0n + kt + 1 - nkc, k2 = in2 ? kt0c + kt + 2 : kt0n + kt + 2 - nkc;
-        if (CLIPK_GEMM_PRIO == 2) __builtin_amdgcn_s_setprio(1);
         rd_a(b, 0); rd_b(b, 0);                 // phase 1: A0 x B0
         if (h1) pst(b ^ 1, cra, in1 ? crb : xrb, k1, 2);
         if (!in1) {
@@ -931,26 +801,19 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
         seg_end(true);
         mm(0, 0);
         G8_BAR();
-        if (CLIPK_GEMM_PRIO == 2) __builtin_amdgcn_s_setprio(1);
         rd_b(b, 1);                             // phase 2: A0 x B1
         if (h2) pst(b, in2 ? cra : xra, crb, k2, 0);
         seg_end();
         mm(0, 1);
         G8_BAR();
-        if (CLIPK_GEMM_PRIO == 2) __builtin_amdgcn_s_setprio(1);
         rd_a(b, 1);                             // phase 3: A1 x B1
         if (h2) {
           pst(b, cra, in2 ? crb : xrb, k2, 3);
-          // the warm-up rides between B1 and A1 of s+2 (wait_ahead counts it): this tile's A
-          // CLIPK_GEMM_WARM steps ahead, clamped to its last K tile
-          warm(cra, kt0c + min(kt + CLIPK_GEMM_WARM, nkc - 1));
         }
         seg_end(true);
         mm(1, 1);
         G8_BAR();
-        if (CLIPK_GEMM_PRIO == 2) __builtin_amdgcn_s_setprio(1);
-        if (NFB == 1) rd_b(b, 0);               // phase 4: A1 x B0
-        if (h2) {
+        if (h2) {                               // phase 4: A1 x B0 (phase 1's B0 fragments)
           pst(b, in2 ? cra : xra, crb, k2, 1);
           wait_ahead();
         } else if (h1) {
@@ -1015,7 +878,7 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
             split8(x0, x1, ah, al);  // (the MFMAs right after it: split_lo8 carries their wait states)
           }
 #pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = mma_split<TWO_TERMS, W16>(bh[j], bl[j], ah, al, acc[i][j]);
+          for (int j = 0; j < TN; ++j) acc[i][j] = mma_split<W16>(bh[j], bl[j], ah, al, acc[i][j]);
         }
       } else
 #pragma unroll
@@ -1034,10 +897,8 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
       if (!last) {
         if constexpr (DEPTH == 2) {
           write_a(cur ^ 1);  // AG: slot cur^1 was last read in step kt-1 (before its barrier)
-          if (!CLIPK_GEMM_NOBAR) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-          }
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __syncthreads();
         } else {
           ring_wait(min(DEPTH - 2, nk - 2 - kt));  // stages kt+2 .. issued after kt+1
           G8_BAR();
@@ -1088,8 +949,8 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
     // bitwise the parts that GEMM's own split would form from the fp32 v). Lanes ec and ec ^ 1 hold
     // the two halves of one 8-column group: they swap (DPP quad_perm [1,0,3,2]), then the even lane
     // stores the group's 16 B of hi parts and the odd lane its 16 B of lo parts.
-    // keep: plain (cache-kept) stores, as the LN-statistics producers' (CLIPK_GEMM_SPOL_LN); else the
-    // chained outputs' policy (CLIPK_GEMM_SPOL_CHAIN)
+    // keep: plain (cache-kept) stores, as the LN-statistics producers' (kStorePolLn); else the
+    // chained outputs' policy (kStorePolChain)
     [[maybe_unused]] auto store_split = [&](__amdgpu_buffer_rsrc_t rs, int m, const float* v, bool keep) {
       static_assert(CW == 4 || !(O_SPLIT || O2_SPLIT), "split-form output: fp32 epilogue lanes (4 columns)");
       if constexpr (CW == 4) {
@@ -1102,20 +963,15 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
         const f16x2 h01 = {(f16)x[0], (f16)x[1]}, h23 = {(f16)x[2], (f16)x[3]};
         const unsigned hu01 = __builtin_bit_cast(unsigned, h01), hu23 = __builtin_bit_cast(unsigned, h23);
         unsigned l01, l23;  // lo = fp16(x - hi) by v_fma_mix (common.h split_lo4; bitwise the cvt form)
-        if constexpr (CLIPK_EPI_MIXSPLIT) {
-          split_lo4(x[0], x[1], x[2], x[3], hu01, hu23, l01, l23);
-        } else {  // A/B: convert, subtract, convert
-          l01 = __builtin_bit_cast(unsigned, (f16x2){(f16)(x[0] - (float)h01[0]), (f16)(x[1] - (float)h01[1])});
-          l23 = __builtin_bit_cast(unsigned, (f16x2){(f16)(x[2] - (float)h23[0]), (f16)(x[3] - (float)h23[1])});
-        }
+        split_lo4(x[0], x[1], x[2], x[3], hu01, hu23, l01, l23);
         const bool odd = (ec & 1) != 0;
         const int s0 = (int)(odd ? hu01 : l01), s1 = (int)(odd ? hu23 : l23);
         const unsigned r0 = (unsigned)__builtin_amdgcn_update_dpp(0, s0, 0xB1, 0xF, 0xF, false);
         const unsigned r1 = (unsigned)__builtin_amdgcn_update_dpp(0, s1, 0xB1, 0xF, 0xF, false);
         const u32x4 d = odd ? (u32x4){r0, r1, l01, l23} : (u32x4){hu01, hu23, r0, r1};
         const int offs = ((m - m0) * g.ldo + (ncol & ~7)) * 4 + (odd ? 16 : 0);
-        if (keep) __builtin_amdgcn_raw_buffer_store_b128(d, rs, offs, 0, CLIPK_GEMM_SPOL_LN);
-        else __builtin_amdgcn_raw_buffer_store_b128(d, rs, offs, 0, CLIPK_GEMM_SPOL_CHAIN);
+        if (keep) __builtin_amdgcn_raw_buffer_store_b128(d, rs, offs, 0, kStorePolLn);
+        else __builtin_amdgcn_raw_buffer_store_b128(d, rs, offs, 0, kStorePolChain);
       }
     };
     // SPF 4: the LayerNorm weight of the next fold, for out2 = split(v * gamma)
@@ -1147,7 +1003,7 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
         const int off = ((m - m0) * g.ldo + ncol) * (int)sizeof(TO);  // rows >= M: out of range, dropped
         // the packed weights' scale undone: exact (a power of 2), so under the LayerNorm fold it
         // rides on the row's rstd (fma(rs * alpha, v, t) == fma(rs, v * alpha, t) bitwise)
-        if constexpr (SPLIT && (!LN_IN || !CLIPK_EPI_MIXSPLIT)) {
+        if constexpr (SPLIT && !LN_IN) {
 #pragma unroll
           for (int c = 0; c < CW; ++c) v[c] *= kSplitAlpha;
         }
@@ -1166,7 +1022,7 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
 #pragma unroll
           for (int c = 0; c < CW; ++c) v[c] = fmaf(rs, v[c], fmaf(nb, csum[c], bia[c]));
         } else if constexpr (LN_IN) {
-          const float rs = lnp[i & 1][q][0] * (SPLIT && CLIPK_EPI_MIXSPLIT ? kSplitAlpha : 1.0f), nb = lnp[i & 1][q][1];
+          const float rs = lnp[i & 1][q][0] * (SPLIT ? kSplitAlpha : 1.0f), nb = lnp[i & 1][q][1];
 #pragma unroll
           for (int c = 0; c < CW; ++c) v[c] = fmaf(rs, v[c], fmaf(nb, csum[c], bia[c]));
         } else if constexpr (HAS_BIAS) {
@@ -1235,7 +1091,7 @@ __global__ __launch_bounds__(WM * WN * 64, DEPTH == 2 ? 2 : 1) void gemm_nt_kern
           // the even lane stores the group's 16 B of hi parts and the odd lane its 16 B of lo parts.
           store_split(ro, m, v, false);
         } else
-        buf_store16<TO, LN_OUT ? CLIPK_GEMM_SPOL_LN : (CHAIN ? CLIPK_GEMM_SPOL_CHAIN : CLIPK_GEMM_SPOL)>(ro, off, v);
+        buf_store16<TO, LN_OUT ? kStorePolLn : (CHAIN ? kStorePolChain : kStorePol)>(ro, off, v);
       }
       if (i + XD < TM) load_ext(i + XD, extq[i % XD]);  // this group's slot is free again
       if (i + 2 < TM) load_ln(i + 2, i & 1);
@@ -1273,12 +1129,15 @@ int gemm_skew();                        // CLIPK_GEMM_SKEW (us), 0 when unset
 // epi the internal epilogue id, lnm the LayerNorm mode; CLIPK_EINVAL for a combination not built
 int presplit_launch(bool w16, int spf, int epi, int lnm, const GemmArgs& g, hipStream_t st);
 
-// BM x 256 ping-pong launch when built in and the shape has >= 2 K tiles (the 256-row forms
-// with an fp32 residual / aux operand would spill: they keep the 2-slot loop)
+// BM x 256 ping-pong launch (persistent) when the shape has >= 2 K tiles (the 256-row forms
+// with an fp32 residual / aux operand would spill: they keep the 2-slot loop). Same-box A/B
+// against the 2-slot loop (profiles/r02m_ab_pingpong.txt): headline step 12.60 -> 12.13 ms,
+// input-grad GEMMs 2.65 -> 2.27 ms/step; staging by global_load_lds with per-lane 64-bit addresses
+// instead of buffer LDS-DMA measured 12.80 ms (the address arithmetic sits in the memory segments).
 template <typename T, typename TO, typename TX, int EPI, int BM, int LNM = 0, int SPF = 0>
 static bool try_pp(const GemmArgs& g, int nwg, hipStream_t st) {
   constexpr bool ext32 = (EPI == CLIPK_EPI_BIAS_RES || EPI == CLIPK_EPI_DQGELU || EPI == EPI_DMUL) && sizeof(TX) == 4;
-  if constexpr (CLIPK_GEMM_PP && (sizeof(T) == 2 || is_split_v<T>) && !(BM == 256 && ext32)) {
+  if constexpr ((sizeof(T) == 2 || is_split_v<T>) && !(BM == 256 && ext32)) {
     if (g.K * (int)sizeof(T) < 2 * GEMM_ROWB) return false;
     hipLaunchKernelGGL((gemm_nt_kernel<T, TO, TX, EPI, BM, 256, 2, 4, true, GEMM_ROWB, 2, false, true, LNM, SPF>),
                        dim3(pp_grid(nwg, num_cus())), dim3(512), 0, st, g);

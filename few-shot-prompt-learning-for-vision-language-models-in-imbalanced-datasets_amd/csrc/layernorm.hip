@@ -1,6 +1,6 @@
 // LayerNorm forward / input-grad backward as wavefront row reductions (HBM-bound).
 // Reference: PromptSRC/clip/model.py:153-159 (fp32 upcast, eps 1e-5, affine).
-// One wave per CLIPK_LN_RPW rows, each row kept in registers (width <= 1024), two-pass mean/variance from
+// One wave per kLnRpw rows, each row kept in registers (width <= 1024), two-pass mean/variance from
 // registers (no E[x^2]-E[x]^2 cancellation); 8 consecutive elements per lane (16-B accesses
 // of 16-bit rows) when the width is a multiple of 512, else 4. The input row (the residual
 // stream) is fp32 or, for the 16-bit text residual stream, the activation dtype (statistics
@@ -16,25 +16,14 @@ constexpr int LN_MAXV = 4;  // 4-element vectors per lane -> width <= 1024
 
 // VW consecutive elements per lane per chunk: 8 (16-B loads of 16-bit rows, 2x16-B of fp32)
 // when width is a multiple of 512, else 4; NC chunks cover width <= 1024.
-// Cache policy knobs (build-time A/B, tools/ab_bench.sh): CLIPK_LN_NT bit 0 = non-temporal
-// row loads, bit 1 = non-temporal stores (16-bit rows).
-#ifndef CLIPK_LN_NT
-#define CLIPK_LN_NT 0
-#endif
+// (Non-temporal row loads / 16-bit stores measured slower: ln_bwd 0.83 -> 0.84 ms/step and the
+// dgelu GEMM after it slower too, profiles/r03m/ab_ln_nt.txt.)
 template <typename T, int VW>
 __device__ __forceinline__ void ldv(const T* p, float* o) {
   if constexpr (VW == 4) {
     load4<T>(p, o);
   } else if constexpr (sizeof(T) == 2) {
-#if CLIPK_LN_NT & 1
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    const t8 v = __builtin_bit_cast(t8, __builtin_nontemporal_load(reinterpret_cast<const u4*>(p)));
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = (float)v[i];
-#else
     load16_f32<T>(p, o);
-#endif
   } else {
     load16_f32<T>(p, o);
     load16_f32<T>(p + 4, o + 4);
@@ -75,16 +64,7 @@ __device__ __forceinline__ void stv(T* p, const float* v) {
   } else if constexpr (VW == 4) {
     store4<T>(p, v[0], v[1], v[2], v[3]);
   } else if constexpr (sizeof(T) == 2) {
-#if CLIPK_LN_NT & 2
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    typedef T t8 __attribute__((ext_vector_type(8)));
-    t8 h;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = (T)v[i];
-    __builtin_nontemporal_store(__builtin_bit_cast(u4, h), reinterpret_cast<u4*>(p));
-#else
     store16_f32<T>(p, v);
-#endif
   } else {
     store16_f32<T>(p, v);
     store16_f32<T>(p + 4, v + 4);
@@ -97,12 +77,7 @@ __device__ __forceinline__ void stv(T* p, const float* v) {
 // (profiles/r02p_ab_ln_rpw.txt, headline step): forward 1 -> 2 rows per wave 0.52 -> 0.50
 // ms/step, 4 rows 0.58; backward 1 row 0.79, 2 rows 0.85, 4 rows 1.06 (its three row streams
 // per row already keep the memory system busy at one row per wave).
-#ifndef CLIPK_LN_RPW
-#define CLIPK_LN_RPW 2
-#endif
-#ifndef CLIPK_LN_RPW_BWD
-#define CLIPK_LN_RPW_BWD 1
-#endif
+constexpr int kLnRpw = 2, kLnRpwBwd = 1;
 template <typename TI, typename TO, int VW, int NC, int RPW>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(int rows, int width, const TI* __restrict__ x,
                                                      int ldx, const int* __restrict__ in_rows,
@@ -307,7 +282,7 @@ static int ln_fwd_launch_rpw(int out_dtype, int rows, int width, const TI* x, in
   CLIPK_CHECK_LAUNCH();
   return CLIPK_OK;
 }
-// Rows per wave: CLIPK_LN_RPW (2) for the 16-bit residual stream; for an fp32 one (PREC fp32 /
+// Rows per wave: kLnRpw (2) for the 16-bit residual stream; for an fp32 one (PREC fp32 /
 // fp32s: twice the bytes per row) knob CLIPK_LN_RPW32 = 1, 2 or 4 (default 2)
 static int ln_rpw32() {
   static int v = -1;
@@ -327,7 +302,7 @@ static int ln_fwd_launch(int out_dtype, int rows, int width, const TI* x, int ld
     if (r == 1) return ln_fwd_launch_rpw<TI, 1>(out_dtype, rows, width, x, ldx, in_rows, gamma, beta, out, ldo, mean, rstd, st);
     if (r == 4) return ln_fwd_launch_rpw<TI, 4>(out_dtype, rows, width, x, ldx, in_rows, gamma, beta, out, ldo, mean, rstd, st);
   }
-  return ln_fwd_launch_rpw<TI, CLIPK_LN_RPW>(out_dtype, rows, width, x, ldx, in_rows, gamma, beta, out, ldo, mean,
+  return ln_fwd_launch_rpw<TI, kLnRpw>(out_dtype, rows, width, x, ldx, in_rows, gamma, beta, out, ldo, mean,
                                             rstd, st);
 }
 
@@ -366,7 +341,7 @@ static int ln_bwd_launch(int rows, int width, const void* dy, int lddy, const TX
                          const int* x_rows, const float* gamma, const float* mean, const float* rstd,
                          const void* dres, bool dres_lp, int lddres, float* dx, void* dx_lp, int lp_dtype,
                          const int* out_rows, int ldo, hipStream_t st) {
-  constexpr int RPW = CLIPK_LN_RPW_BWD;
+  constexpr int RPW = kLnRpwBwd;
   dim3 grid((rows + 4 * RPW - 1) / (4 * RPW)), block(256);
   const TD* d = (const TD*)dy;
   const bool v8 = width % 512 == 0 && ldx % 8 == 0 && ldo % 8 == 0 && lddy % 8 == 0 && (!dres || lddres % 8 == 0);

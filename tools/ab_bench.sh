@@ -1,7 +1,8 @@
 #!/bin/bash
 # A/B of library variants on the headline bench (GPU box): tools/ab_bench.sh tag1 tag2 ...
 # ("base" = the in-tree libclipk.so; "env:NAME=VAL[,NAME=VAL]" = the in-tree library with those
-# runtime knobs; others build_ab/<tag>/libclipk.so). Two interleaved rounds; one summary line
+# runtime knobs; others build_ab/<tag>/libclipk.so, a -D build by tools/build_variant.sh of a
+# switch added for the experiment). Two interleaved rounds; one summary line
 # per run in gpurun_out/ab.log.
 R=$(pwd)
 mkdir -p gpurun_out

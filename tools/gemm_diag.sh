@@ -1,6 +1,7 @@
 #!/bin/bash
-# GEMM loop diagnostics on the GPU box: the text-shape yardstick on the in-tree library and on
-# diagnostic variants (tools/build_variant.sh), cold (A rotated through HBM) and hot.
+# GEMM loop diagnostics on the GPU box: the text-shape yardstick, cold (A rotated through HBM) and
+# hot, on the in-tree library ("base", "cfgN", "env:NAME=VAL") or on a -D build of it
+# (build_ab/<tag>/libclipk.so from tools/build_variant.sh; the source defines no such switches).
 #   tools/gemm_diag.sh tag1 tag2 ...   -> gpurun_out/gemm_diag.log
 R=$(pwd)
 mkdir -p gpurun_out
