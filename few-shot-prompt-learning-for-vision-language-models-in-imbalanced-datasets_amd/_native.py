@@ -42,6 +42,7 @@ EPI_BIAS, EPI_BIAS_RES, EPI_BIAS_QGELU, EPI_DQGELU, EPI_NONE = 0, 1, 2, 3, 4
 A_QGELU = 0x100  # OR-ed into epi: the GEMM consumes quickgelu(A) (include/clipk.h)
 QGELU_DERIV = 0x200  # OR-ed into epi: out2 = quickgelu' (EPI_BIAS_QGELU) / aux is quickgelu' (EPI_DQGELU)
 OUT_SPLIT, A_SPLIT = 0x400, 0x800  # PREC fp32s pre-split operands (include/clipk.h)
+ADAM_ADAM, ADAM_ADAMW, ADAM_AMSGRAD = 0, 1, 2  # clipk_adam_step_multi modes
 PROF_NONE, PROF_GEMM_FC, PROF_GEMM_ALL, PROF_ATTN, PROF_LN, PROF_GEMM_DGELU = 0, 1, 2, 3, 4, 5
 
 _P = ctypes.c_void_p
@@ -106,6 +107,7 @@ SIGNATURES = {
     "clipk_sgd_step_multi": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _F, _P]),
     "clipk_sgd_step_multi_scaled": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P]),
     "clipk_sgd_step_multi_if": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _I, _P]),
+    "clipk_adam_step_multi": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _D, _I, _F, _P, _I, _P]),
     "clipk_cast": (_I, [_I, _L, _P, _P, _P]),
     "clipk_rows_copy": (_I, [_I, _I, _P, _P, _P, _P, _P]),
     "clipk_vit_embed_ln_vpt": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),

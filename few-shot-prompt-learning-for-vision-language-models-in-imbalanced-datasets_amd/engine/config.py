@@ -108,7 +108,8 @@ def get_cfg_default() -> CfgNode:
         "MODEL": {"INIT_WEIGHTS": "", "BACKBONE": {"NAME": "ViT-B/16"}, "WEIGHTS_PATH": "",
                   "SYNTH_FP16": False},
         "OPTIM": {"NAME": "sgd", "LR": 0.002, "WEIGHT_DECAY": 5e-4, "MOMENTUM": 0.9,
-                  "SGD_DAMPNING": 0, "SGD_NESTEROV": False, "LR_SCHEDULER": "cosine",
+                  "SGD_DAMPNING": 0, "SGD_NESTEROV": False, "ADAM_BETA1": 0.9, "ADAM_BETA2": 0.999,
+                  "LR_SCHEDULER": "cosine", "STEPSIZE": (-1,), "GAMMA": 0.1,
                   "MAX_EPOCH": 10, "WARMUP_EPOCH": -1, "WARMUP_TYPE": "linear",
                   "WARMUP_CONS_LR": 1e-5, "WARMUP_MIN_LR": 1e-5, "WARMUP_RECOUNT": True},
         "TRAIN": {"PRINT_FREQ": 10, "CHECKPOINT_FREQ": 0},

@@ -479,6 +479,43 @@ def sgd_step_multi(ps, gs, bufs, lr, momentum, weight_decay, has_bufs, grad_scal
             N.call("clipk_sgd_step_multi_scaled", *args, float(grad_scale), _stream())
 
 
+ADAM_MODES = {"adam": N.ADAM_ADAM, "adamw": N.ADAM_ADAMW, "amsgrad": N.ADAM_AMSGRAD}
+
+
+def adam_step_multi(ps, gs, ms, vs, vmaxs, steps, parities, lr, beta1, beta2, eps, weight_decay, mode,
+                    grad_scale=1.0, guard=None):
+    """clipk_adam_step_multi: one launch per 16 tensors (fp32, contiguous, on one device). mode
+    "adam" / "adamw" / "amsgrad" (vmaxs: the max_exp_avg_sq tensors, else None); steps[k]: the
+    tensor's two int32 device step counters, parities[k] the one this call reads (the caller flips
+    it afterwards); grad_scale multiplies every gradient; guard = (int32 device flags, mask): the
+    update and the step count's advance are skipped on the device when flags[0] & mask."""
+    amsgrad = mode == "amsgrad"
+    lists = [ps, gs, ms, vs] + ([vmaxs] if amsgrad else [])
+    if amsgrad and vmaxs is None:
+        raise N.ClipkError("adam_step_multi: amsgrad needs the max_exp_avg_sq tensors")
+    if any(len(l) != len(ps) for l in lists + [steps, parities]):
+        raise N.ClipkError("adam_step_multi: lists of different lengths")
+    for k, p in enumerate(ps):
+        for l in lists:
+            _need(l[k], "adam_step_multi tensor", torch.float32)
+            if l[k].device != p.device or l[k].numel() != p.numel():
+                raise N.ClipkError("adam_step_multi: a parameter's tensors differ in device or size")
+        _need(steps[k], "step counters", torch.int32)
+        if steps[k].numel() != 2 or steps[k].device != ps[0].device or p.device != ps[0].device:
+            raise N.ClipkError("adam_step_multi: two int32 step counters per tensor, everything on one device")
+    for i in range(0, len(ps), 16):
+        c = len(ps[i:i + 16])
+        VP = ctypes.c_void_p * c
+        ptrs = [VP(*[t.data_ptr() for t in l[i:i + 16]]) for l in lists]
+        if not amsgrad:
+            ptrs.append(None)
+        N.call("clipk_adam_step_multi", c, *ptrs, (ctypes.c_long * c)(*[t.numel() for t in ps[i:i + 16]]),
+               VP(*[t.data_ptr() for t in steps[i:i + 16]]), (ctypes.c_int * c)(*parities[i:i + 16]),
+               float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), ADAM_MODES[mode],
+               float(grad_scale), _p(guard[0]) if guard is not None else None,
+               int(guard[1]) if guard is not None else 0, _stream())
+
+
 def cast(x, dtype):
     y = torch.empty(x.shape, device=x.device, dtype=dtype)
     N.call("clipk_cast", DT[dtype], x.numel(), _p(x.contiguous()), _p(y), _stream())

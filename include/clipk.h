@@ -26,6 +26,9 @@
  *   clipk_meta_net_*      CoCoOp Meta-Net Linear-ReLU-Linear (cocoop.py:139-143,182-185)
  *   clipk_sgd_step        torch.optim.SGD momentum/wd step (dassl optim/optimizer.py:105-113)
  *   clipk_sgd_step_multi  the same over a param group's tensors in one launch
+ *   clipk_adam_step_multi torch.optim.Adam / AdamW / Adam(amsgrad=True) step over a param
+ *                         group's tensors in one launch (dassl optim/optimizer.py adam,
+ *                         amsgrad, adamw)
  *   clipk_text_*          TextEncoder.forward + its input-grad backward (coop.py:195-205)
  *   clipk_vit_forward     VisionTransformer.forward (model.py:401-431), frozen, fwd only
  */
@@ -413,6 +416,31 @@ int clipk_sgd_step_multi_scaled(int count, float* const* p, const float* const* 
 int clipk_sgd_step_multi_if(int count, float* const* p, const float* const* g, float* const* buf,
                             const long* n, const int* has_buf, float lr, float momentum,
                             float weight_decay, float grad_scale, const int* guard, int mask, void* stream);
+
+/* clipk_adam_step_multi modes */
+enum { CLIPK_ADAM_ADAM = 0, CLIPK_ADAM_ADAMW = 1, CLIPK_ADAM_AMSGRAD = 2 };
+/* torch.optim.Adam / AdamW step (non-capturable single-tensor semantics) over up to 16 tensors of
+ * one param group in one launch: p[k], g[k], m[k] (exp_avg), v[k] (exp_avg_sq) and, for
+ * CLIPK_ADAM_AMSGRAD, vmax[k] (max_exp_avg_sq; vmax may be NULL otherwise) of n[k] floats; host
+ * arrays of device pointers. With g' = grad_scale * g (rounded on its own; 1.0 is bitwise the
+ * unscaled update):
+ *   ADAM / AMSGRAD  g' += wd * p                      ADAMW  p *= 1 - lr * wd
+ *   m = beta1 m + (1 - beta1) g'      v = beta2 v + (1 - beta2) g'^2      [vmax = max(vmax, v)]
+ *   p -= lr / (1 - beta1^t) * m / (sqrt(v or vmax) / sqrt(1 - beta2^t) + eps)
+ * 1 - beta^t is formed in double on the device and the step size rounded to fp32.
+ * The step count is device state, per tensor: step[k] points at two int32 (both 0 for fresh
+ * state). The launch reads t - 1 = step[k][parity[k]] and writes t to step[k][parity[k] ^ 1]; the
+ * caller flips parity[k] (0 / 1) after every call that names the tensor, so the count of the
+ * last call is step[k][next parity].
+ * guard (may be NULL): when guard[0] & mask != 0, read on the device, the whole update is skipped
+ * -- p, m, v, vmax untouched and the count carried over unchanged (the parity still flips).
+ * CLIPK_EINVAL: count outside 1..16, a null pointer, a parity other than 0 / 1, mode out of
+ * range, beta outside [0, 1), eps, lr or weight_decay < 0; CLIPK_ESHAPE: n[k] < 0. */
+int clipk_adam_step_multi(int count, float* const* p, const float* const* g, float* const* m,
+                          float* const* v, float* const* vmax, const long* n, int* const* step,
+                          const int* parity, double lr, double beta1, double beta2, double eps,
+                          double weight_decay, int mode, float grad_scale, const int* guard, int mask,
+                          void* stream);
 /* Status word hand-off (PREC fp32s overflow flags, clipk_encoder_set_status): host_word[0] =
  * flags[0], then flags[0] = 0, in one stream-ordered launch; host_word is host-visible memory
  * (pinned). The caller synchronises the stream (or an event after it) before reading it. */
