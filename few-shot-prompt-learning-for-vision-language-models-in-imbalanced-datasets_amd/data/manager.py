@@ -129,11 +129,27 @@ def _collate(items):
             "n_global": items[0]["n_global"], "n_local": items[0]["n_local"]}
 
 
-class GpuLoader:
-    """Iterates a host DataLoader of decoded images and applies the GPU transform."""
+def two_views(cfg) -> bool:
+    """Whether the trainer's objective contrasts two augmented views of each training image:
+    CoOp with LOSS_TYPE "simclr" (coop.py:370-377) and IVLP with SIMCLR_ALPHA > 0
+    (independentVL.py:300-316). Their training batches carry "img1" / "img2"."""
+    name = cfg.TRAINER.NAME
+    if name == "CoOp":
+        return cfg.TRAINER.COOP.get("LOSS_TYPE", "ce") == "simclr"
+    if name == "IVLP":
+        return float(cfg.TRAINER.IVLP.get("SIMCLR_ALPHA", 0.0)) > 0.0
+    return False
 
-    def __init__(self, loader, transform, device):
-        self.loader, self.transform, self.device = loader, transform, device
+
+class GpuLoader:
+    """Iterates a host DataLoader of decoded images and applies the GPU transform. views=2:
+    two independent draws of the transform per image as "img1" / "img2" (the two halves of one
+    preprocessing output), "img" an alias of "img1" (the same tensor)."""
+
+    def __init__(self, loader, transform, device, views=1):
+        if views not in (1, 2):
+            raise ValueError(f"views must be 1 or 2, got {views}")
+        self.loader, self.transform, self.device, self.views = loader, transform, device, views
 
     def __len__(self):
         return len(self.loader)
@@ -141,7 +157,11 @@ class GpuLoader:
     def __iter__(self):
         for b in self.loader:
             out = dict(b)
-            out["img"] = self.transform(b["img"])
+            if self.views == 2:
+                out["img1"], out["img2"] = self.transform(b["img"], views=2)
+                out["img"] = out["img1"]
+            else:
+                out["img"] = self.transform(b["img"])
             out["label"] = b["label"].to(self.device, non_blocking=True)
             yield out
 
@@ -164,7 +184,7 @@ class DataManager:
             DataLoader(DatasetWrapper(train, reader), batch_sampler=self.train_batch_sampler, num_workers=nw,
                        collate_fn=_collate, pin_memory=False),
             GpuTransform(cfg, is_train=True, device=self.device, generator=augment_generator(self.replicated)),
-            self.device)
+            self.device, views=2 if two_views(cfg) else 1)
 
         def test_loader(data):
             if not data:

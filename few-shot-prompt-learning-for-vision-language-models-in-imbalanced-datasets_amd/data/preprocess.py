@@ -147,10 +147,12 @@ def _tables(plans, shapes):
     return np.asarray(desc, np.int64), np.concatenate(tabs).astype(np.int32), tmp_off
 
 
-def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8=False):
+def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8=False, src_index=None):
     """images: list of uint8 HWC (RGB) numpy arrays or CPU/GPU torch tensors; plans: Plan
     per image (all with the same S). Returns fp32 [B, 3, S, S] normalised on `device` (or
-    the uint8 resampled pixels [B, 3, S, S] when out_uint8, for bit-exact checks)."""
+    the uint8 resampled pixels [B, 3, S, S] when out_uint8, for bit-exact checks).
+    src_index: plans[k] reads images[src_index[k]] (B = len(plans) outputs from fewer source
+    images, each uploaded once: the two views of a SimCLR batch); None: plans[k] reads images[k]."""
     dev = torch.device(device)
     S = plans[0].S
     if any(p.S != S for p in plans):
@@ -159,13 +161,17 @@ def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8
     for t in ts:
         if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
             raise ValueError("images must be uint8 [H, W, 3]")
-    shapes = [(int(t.shape[0]), int(t.shape[1])) for t in ts]
+    src_index = [int(k) for k in (range(len(plans)) if src_index is None else src_index)]
+    if len(src_index) != len(plans) or any(not 0 <= k < len(ts) for k in src_index):
+        raise ValueError("src_index must name one source image per plan")
+    img_shapes = [(int(t.shape[0]), int(t.shape[1])) for t in ts]
+    shapes = [img_shapes[k] for k in src_index]  # of the image each plan reads
     for p, (H, W) in zip(plans, shapes):
         if p.x0 < 0 or p.y0 < 0 or p.x0 + p.w > W or p.y0 + p.h > H or p.rw < p.ox + S or p.rh < p.oy + S:
             raise ValueError("plan window outside the image")
     desc, tab, tmp_elems = _tables(plans, shapes)
-    offs = np.cumsum([0] + [H * W * 3 for H, W in shapes])
-    desc[:, 0] = offs[:-1]
+    offs = np.cumsum([0] + [H * W * 3 for H, W in img_shapes])
+    desc[:, 0] = offs[:-1][src_index]
     src = torch.cat([t.reshape(-1) for t in ts]).to(dev, non_blocking=True)
     d_desc = torch.from_numpy(desc).to(dev)
     d_tab = torch.from_numpy(tab).to(dev)
@@ -213,6 +219,22 @@ class GpuTransform:
             p.flip = bool(torch.rand(1, generator=self.generator) < 0.5)
         return p
 
-    def __call__(self, images):
-        plans = [self.plan(int(im.shape[1]), int(im.shape[0])) for im in images]
-        return preprocess_batch(images, plans, self.mean, self.std, self.device)
+    def plans(self, sizes, views=1):
+        """Plans for images of the given (w, h) sizes, `views` draws each, image-major from the
+        transform's generator: image 0 view 1, image 0 view 2, image 1 view 1, ..."""
+        return [self.plan(w, h) for w, h in sizes for _ in range(views)]
+
+    def __call__(self, images, views=1):
+        """views=1: the transformed batch [B, 3, S, S]. views=2 (SimCLR): two independent draws of
+        the transform per image -> (x1, x2), the two halves of ONE [2B, 3, S, S] output (no copy);
+        the pixels are uploaded once and one resample launch covers both views."""
+        sizes = [(int(im.shape[1]), int(im.shape[0])) for im in images]
+        if views == 1:
+            return preprocess_batch(images, self.plans(sizes), self.mean, self.std, self.device)
+        if views != 2:
+            raise ValueError(f"views must be 1 or 2, got {views}")
+        B = len(sizes)
+        drawn = self.plans(sizes, 2)  # image-major
+        out = preprocess_batch(images, drawn[0::2] + drawn[1::2], self.mean, self.std, self.device,
+                               src_index=list(range(B)) * 2)
+        return out[:B], out[B:]

@@ -1,6 +1,7 @@
 """Synthetic DataManager with the Dassl surface the trainers read
 (``dm.dataset.classnames``, ``dm.dataset.lab2cname``, ``dm.train_loader_x``,
-``dm.test_loader``; batches are dicts {"img", "label"}; data_manager.py:55-162,234-263).
+``dm.test_loader``; batches are dicts {"img", "label"}, plus {"img1", "img2"} with
+``two_views``; data_manager.py:55-162,234-263).
 
 Images are seeded U[0,1) CLIP-normalised tensors, generated once and
 kept resident on the device (no decode/augment in the timed region). Labels follow the
@@ -22,10 +23,17 @@ class _Dataset:
         self.num_classes = len(classnames)
 
 
+VIEW2_SEED = 500_000  # offset of the second view's image seed from its batch's (two_views)
+
+
 class SyntheticDataManager:
     def __init__(self, n_cls, resolution, batch_size, n_batches=2, test_batch=100, n_test=0,
-                 per_class_shots=None, device="cuda", seed=1, rank=0, n_test_device=0):
-        """n_test: test images made on the host (numpy RandomState, as the fixtures);
+                 per_class_shots=None, device="cuda", seed=1, rank=0, n_test_device=0, two_views=False):
+        """two_views: every training batch also carries "img1" (the same tensor as "img") and
+        "img2", a second set of images drawn from the batch's seed + VIEW2_SEED (the SimCLR
+        objectives, data/manager.py two_views; synthetic noise has no augmentation to share, so
+        the views are two independent draws).
+        n_test: test images made on the host (numpy RandomState, as the fixtures);
         n_test_device: a large test set drawn directly in HBM (torch generator on the
         device; U[0,1) then CLIP-normalised), e.g. the 50,000-image eval timing set of
         SURVEY §8(d) -- 30 GB at 224 px fp32, resident, every image distinct."""
@@ -40,8 +48,12 @@ class SyntheticDataManager:
         for i in range(n_batches):
             img = synth.make_images(batch_size, resolution, seed=seed + 31 * i + 7919 * rank)
             lab = rs.choice(pool, size=batch_size).astype(np.int64)
-            self.train_loader_x.append({"img": torch.from_numpy(img).to(dev),
-                                        "label": torch.from_numpy(lab).to(dev)})
+            batch = {"img": torch.from_numpy(img).to(dev), "label": torch.from_numpy(lab).to(dev)}
+            if two_views:
+                img2 = synth.make_images(batch_size, resolution, seed=seed + 31 * i + 7919 * rank + VIEW2_SEED)
+                batch["img1"] = batch["img"]
+                batch["img2"] = torch.from_numpy(img2).to(dev)
+            self.train_loader_x.append(batch)
         self.test_loader = []
         for i in range(0, n_test, test_batch):
             b = min(test_batch, n_test - i)

@@ -148,6 +148,11 @@ def get_cfg_default() -> CfgNode:
                    # OVERLAP_VISION: CoOp runs the frozen image encoder on a side stream while the
                    # text encoder (independent of the images) runs on the main one
                    "OVERLAP_VISION": True,
+                   # FUSED_SIMCLR: the SimCLR objective (CoOp LOSS_TYPE simclr, IVLP SIMCLR_ALPHA) on
+                   # the native NT-Xent kernel (clipk_ntxent_loss), and CoOp's two views scored against
+                   # ONE encode of the class prompts instead of one per view. Off: the torch
+                   # composition and the reference's two forward_once calls, bit for bit as before
+                   "FUSED_SIMCLR": False,
                    # PREFETCH_VISION: CoCoOp starts the next batch's image encoder (frozen) on a side
                    # stream between a step's forward and backward (the loop names the next batch)
                    "PREFETCH_VISION": True,

@@ -436,6 +436,29 @@ def ce_loss_reduce(logits, labels, alpha=None, gamma=2.0, focal=False, grad=True
     return loss, dl
 
 
+def ntxent_loss(a, b, temperature=0.07, grad=True, grad_scale=1.0):
+    """clipk_ntxent_loss: NT-Xent of the two views a, b (fp32 [n, D]) -> (loss [], da, db) with
+    da / db = grad_scale * d loss / d a, b (None when not grad). 1 <= n <= 512."""
+    _need(a, "a", torch.float32)
+    _need(b, "b", torch.float32)
+    if a.dim() != 2 or b.shape != a.shape:
+        raise N.ClipkError(f"a and b must be [n, D] of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if b.device != a.device:
+        raise N.ClipkError("a and b must be on one device")
+    n, D = a.shape
+    if not 1 <= n <= 512 or D < 1:
+        raise N.ClipkError(f"ntxent_loss needs 1 <= n <= 512 and D >= 1, got n = {n}, D = {D}")
+    if not temperature > 0:
+        raise N.ClipkError(f"temperature must be positive, got {temperature}")
+    ws = torch.empty(N.load().clipk_ntxent_ws_bytes(n, D), dtype=torch.uint8, device=a.device)
+    loss = torch.empty((), device=a.device)
+    da = torch.empty_like(a) if grad else None
+    db = torch.empty_like(b) if grad else None
+    N.call("clipk_ntxent_loss", n, D, _p(a), _p(b), float(temperature), float(grad_scale), _p(loss), _p(da), _p(db),
+           _p(ws), _stream())
+    return loss, da, db
+
+
 def status_take(flags, host_word):
     """clipk_status_take: flags -> host_word (pinned int32), flags cleared (stream-ordered)."""
     N.call("clipk_status_take", _p(flags), _p(host_word), _stream())

@@ -139,6 +139,30 @@ class CrossEntropyFn(torch.autograd.Function):
         return dl, None, None, None, None, None
 
 
+class NTXentFn(torch.autograd.Function):
+    """NT-Xent of two views (LogitsNTXentLoss, coop.py:72-123; ImageNTXentLoss, independentVL.py:
+    73-112), loss and both views' gradients from the forward call (clipk_ntxent_loss)."""
+
+    @staticmethod
+    def forward(ctx, a, b, temperature):
+        grad = a.requires_grad or b.requires_grad
+        loss, ctx.da, ctx.db = ops.ntxent_loss(a.contiguous(), b.contiguous(), temperature, grad=grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        # (as CrossEntropyFn.backward: no multiply launch for backward_unit's cached 1.0)
+        if g.data_ptr() == unit_grad(g.device).data_ptr():
+            return ctx.da, ctx.db, None
+        return ctx.da * g, ctx.db * g, None
+
+
+def ntxent_fused_ok(a, b):
+    """The shapes and types clipk_ntxent_loss takes: CUDA fp32 [n, D] views, 1 <= n <= 512."""
+    return (a.is_cuda and b.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32
+            and a.dim() == 2 and a.shape == b.shape and 1 <= a.shape[0] <= 512 and a.shape[1] >= 1)
+
+
 _UNIT = {}
 
 

@@ -121,9 +121,10 @@ class CustomCLIP(ImageFeatureSchedule, nn.Module):
         self.logit_scale_value = clip_model.logit_scale_value
         self.dtype = clip_model.dtype
         self.loss_type = cfg.TRAINER.COOP.get("LOSS_TYPE", "ce")
+        self.fused_simclr = bool(cfg.get("NATIVE", {}).get("FUSED_SIMCLR", False))
         if self.loss_type == "simclr":
             print(">> Using LogitsNTXentLoss (logit-based simclr)!")
-            self.criterion_simclr = LogitsNTXentLoss(temperature=0.07)
+            self.criterion_simclr = LogitsNTXentLoss(temperature=0.07, fused=self.fused_simclr)
         elif self.loss_type == "ce":
             print(">> Using CE Loss!")
             self.criterion_ce = CrossEntropyLoss()
@@ -183,7 +184,36 @@ class CustomCLIP(ImageFeatureSchedule, nn.Module):
             imf = join()
         return CosineLogitsFn.apply(imf, txt, self.logit_scale_value, 0, self.prompt_learner.n_cls)
 
+    def _image_features_start(self, image):
+        """forward_once's image-feature schedule for one view, as a join() -> features: cached,
+        on the side stream (NATIVE.OVERLAP_VISION, training), or inline."""
+        imf = self.cached_image_features(image)
+        if imf is None:
+            if (image.is_cuda and self.cfg.get("NATIVE", {}).get("OVERLAP_VISION", False)
+                    and (self.training or torch.is_grad_enabled())):
+                return self.image_features_async(image)
+            imf = self.image_features(image)
+        return lambda: imf
+
+    def forward_two_views(self, img1, img2):
+        """Both views' logits from ONE encode of the class prompts (NATIVE.FUSED_SIMCLR). The
+        reference's two forward_once calls (coop.py:370-377) encode the same ctx twice; the text
+        features do not depend on the images, so autograd sums the two views' d txt into one text
+        backward (and a class-sharded run all-gathers once). Both image encodes are queued (side
+        stream: beside the text encoder) before the text encoder."""
+        join1 = self._image_features_start(img1)
+        join2 = self._image_features_start(img2)
+        if not self.training and not torch.is_grad_enabled():
+            txt = self._cached_text_features()
+        else:
+            txt = self.text_features()
+        n_cls = self.prompt_learner.n_cls
+        return (CosineLogitsFn.apply(join1(), txt, self.logit_scale_value, 0, n_cls),
+                CosineLogitsFn.apply(join2(), txt, self.logit_scale_value, 0, n_cls))
+
     def forward(self, img1, lbl=None, img2=None):
+        if self.loss_type == "simclr" and self.fused_simclr:
+            return self.criterion_simclr(*self.forward_two_views(img1, img2))
         if self.loss_type == "simclr":
             return self.criterion_simclr(self.forward_once(img1), self.forward_once(img2))
         if self.loss_type in ("ce", "focal"):

@@ -28,7 +28,7 @@ from ..engine.trainer import TrainerX, load_clip
 from ..engine.optim import build_optimizer, build_lr_scheduler
 from ..engine.metrics import LossSummary
 from ..clip.model import TextEncodeFn, DeepTextEncodeFn, PromptedVisionFn
-from ._fns import PromptAssembleFn, CrossEntropyFn
+from ._fns import PromptAssembleFn, CrossEntropyFn, NTXentFn, ntxent_fused_ok
 from .losses import focal_alpha
 from .prompt_base import init_prompts, grads_finite
 
@@ -175,6 +175,7 @@ class IVLPCustomCLIP(_DeepCLIP):
         self.alpha = torch.tensor(alpha, dtype=torch.float32, device=clip_model.logit_scale.device) \
             if alpha is not None else None
         self.simclr_alpha = float(sec.get("SIMCLR_ALPHA", 0.0))
+        self.fused_simclr = bool(cfg.get("NATIVE", {}).get("FUSED_SIMCLR", False))
 
     def criterion(self, logits, y):
         return CrossEntropyFn.apply(logits, y, self.alpha, 2.0, self.focal)
@@ -186,12 +187,15 @@ class IVLPCustomCLIP(_DeepCLIP):
         total = self.criterion(logits, label) if label is not None else 0.0
         if image2 is not None and self.simclr_alpha > 0.0:
             img2 = F.normalize(self.image_features(image2), dim=-1)
-            total = total + self.simclr_alpha * image_ntxent(img, img2)
+            total = total + self.simclr_alpha * image_ntxent(img, img2, fused=self.fused_simclr)
         return total
 
 
-def image_ntxent(z1, z2, temperature=0.07):
-    """ImageNTXentLoss (independentVL.py:73-112), vectorised: positives z1[i] <-> z2[i]."""
+def image_ntxent(z1, z2, temperature=0.07, fused=False):
+    """ImageNTXentLoss (independentVL.py:73-112), vectorised: positives z1[i] <-> z2[i]. fused
+    (NATIVE.FUSED_SIMCLR): the native clipk_ntxent_loss where it takes the inputs."""
+    if fused and ntxent_fused_ok(z1, z2):
+        return NTXentFn.apply(z1, z2, temperature)
     z = torch.cat([F.normalize(z1, dim=1), F.normalize(z2, dim=1)], 0)
     n2 = z.shape[0]
     n = n2 // 2

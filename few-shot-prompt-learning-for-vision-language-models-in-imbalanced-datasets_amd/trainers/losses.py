@@ -2,8 +2,9 @@
 
 CE and the class-frequency-weighted focal loss run as one fused HIP kernel (forward
 and dlogits together, ``clipk_ce_loss``). The logit-space NT-Xent loss (CoOp
-LOSS_TYPE "simclr") operates on the tiny [2B, 2B] similarity of L2-normalised logits
-and is composed from torch ops (vectorised form of the reference's per-row loop).
+LOSS_TYPE "simclr") operates on the tiny [2B, 2B] similarity of L2-normalised logits:
+composed from torch ops (vectorised form of the reference's per-row loop), or, with
+``fused`` (NATIVE.FUSED_SIMCLR), the native ``clipk_ntxent_loss`` (NTXentFn).
 """
 from __future__ import annotations
 
@@ -11,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._fns import CrossEntropyFn
+from ._fns import CrossEntropyFn, NTXentFn, ntxent_fused_ok
 
 
 class CrossEntropyLoss(nn.Module):
@@ -45,11 +46,14 @@ class MultiClassFocalLoss(nn.Module):
 
 
 class LogitsNTXentLoss(nn.Module):
-    def __init__(self, temperature=0.07):
+    def __init__(self, temperature=0.07, fused=False):
         super().__init__()
         self.temperature = temperature
+        self.fused = fused
 
     def forward(self, logits1, logits2):
+        if self.fused and ntxent_fused_ok(logits1, logits2):
+            return NTXentFn.apply(logits1, logits2, self.temperature)
         z = torch.cat([F.normalize(logits1, dim=1), F.normalize(logits2, dim=1)], 0)
         n2 = z.shape[0]
         n = n2 // 2

@@ -23,6 +23,8 @@
  *                         (coop.py:356-363, cocoop.py:238-251)
  *   clipk_ce_loss         nn.CrossEntropyLoss / MultiClassFocalLoss fwd+bwd
  *                         (coop.py:131-163,324; cocoop.py:66-101,233)
+ *   clipk_ntxent_loss     LogitsNTXentLoss / ImageNTXentLoss fwd+bwd
+ *                         (coop.py:72-123; independentVL.py:73-112)
  *   clipk_meta_net_*      CoCoOp Meta-Net Linear-ReLU-Linear (cocoop.py:139-143,182-185)
  *   clipk_sgd_step        torch.optim.SGD momentum/wd step (dassl optim/optimizer.py:105-113)
  *   clipk_sgd_step_multi  the same over a param group's tensors in one launch
@@ -379,6 +381,22 @@ int clipk_ce_loss(int B, int C, const float* logits, const int64_t* labels, cons
 int clipk_ce_loss_reduce(int B, int C, const float* logits, const int64_t* labels, const float* alpha,
                          float gamma, int focal, float grad_scale, int reduction, float* row_loss,
                          float* loss, float* dlogits, void* stream);
+
+/* NT-Xent (SimCLR) loss of two views a, b (fp32 [n, D], contiguous), forward and gradient:
+ * LogitsNTXentLoss on the two views' logits (coop.py:72-123) and ImageNTXentLoss on their image
+ * features (independentVL.py:73-112). With N = 2n, rows x_0..x_{N-1} = the rows of a then of b and
+ * p(i) = (i + n) mod N:  z_i = x_i / max(|x_i|, 1e-12),  s_ij = z_i . z_j / temperature,
+ *   loss[0] = (1/N) sum_i ( log sum_{j != i} exp(s_ij) - s_{i,p(i)} ),
+ * da / db [n, D] = grad_scale * d loss / d a, b; both NULL: forward only, no gradient work is
+ * launched. fp32 products and sums throughout, every sum in a fixed order (bitwise reproducible,
+ * no atomics); 3 launches either way (csrc/ntxent.hip). n = 1 gives loss 0 and zero gradients.
+ * ws: caller workspace of clipk_ntxent_ws_bytes(n, D) bytes (0 for a shape out of range); no
+ * allocation or synchronisation inside. Any D >= 1, 1 <= n <= 512 (else CLIPK_ESHAPE);
+ * CLIPK_EINVAL: a, b, loss or ws null, only one of da / db given, temperature <= 0. */
+size_t clipk_ntxent_ws_bytes(int n, int D);
+int clipk_ntxent_loss(int n, int D, const float* a, const float* b, float temperature,
+                      float grad_scale, float* loss, float* da, float* db,
+                      void* ws, void* stream);
 
 /* CoCoOp Meta-Net: h = relu(x W1^T + b1); y = h W2^T + b2. x [B,V], W1 [Hd,V], W2 [Wd,Hd].
  * The CLIP widths (V % 256 == 0, V <= 1024, Hd <= 64, x / W1 16-B aligned) take the
