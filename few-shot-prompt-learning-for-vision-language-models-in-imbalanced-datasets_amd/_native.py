@@ -99,6 +99,8 @@ SIGNATURES = {
     "clipk_cosine_logits_bwd": (_I, [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
     "clipk_ce_loss": (_I, [_I, _I, _P, _P, _P, _F, _I, _F, _P, _P, _P]),
     "clipk_ce_loss_reduce": (_I, [_I, _I, _P, _P, _P, _F, _I, _F, _I, _P, _P, _P, _P]),
+    "clipk_ce_loss_mix": (_I, [_I, _I, _P, _P, _P, _F, _P, _F, _I, _F, _I, _P, _P, _P, _P]),
+    "clipk_mixup_images": (_I, [_I, _L, _P, _P, _P, _P, _F, _F, _P, _P]),
     "clipk_ntxent_ws_bytes": (_S, [_I, _I]),
     "clipk_ntxent_loss": (_I, [_I, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "clipk_meta_net_fwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -28,6 +28,9 @@ transform's own (``augment_generator``), not from torch's global RNG -- that one
 across ranks every epoch for the sampler stream, so drawing crops from it would give rank r's
 k-th image the same crop as rank 0's. Data parallel: one stream per rank (seed + rank);
 replicated batches: one stream shared by every rank (they must preprocess identically).
+IVLP's mixup draws (``mixup``, ``draw_mix``: lam and the batch permutation) come from the same
+generator after the batch's crop draws, so replicated ranks draw the same mix and sharded ranks
+each mix their local batch.
 """
 from __future__ import annotations
 
@@ -35,7 +38,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset, Sampler
 
-from .. import dist
+from .. import dist, ops
 from .fewshot import build_sampler
 
 
@@ -141,15 +144,41 @@ def two_views(cfg) -> bool:
     return False
 
 
+def mixup(cfg) -> bool:
+    """Whether the training loader mixes its batches (mixup_data, independentVL.py:435-449): IVLP
+    with USE_MIXUP and NATIVE.MIXUP. The SimCLR batch form wins (IVLP.parse_batch_train's order
+    would otherwise hide it): never together with two_views(cfg)."""
+    if cfg.TRAINER.NAME != "IVLP" or two_views(cfg):
+        return False
+    return bool(cfg.TRAINER.IVLP.get("USE_MIXUP", False)) and bool(cfg.get("NATIVE", {}).get("MIXUP", False))
+
+
+def draw_mix(alpha, n, generator=None):
+    """mixup_data's draws for a batch of n: lam ~ Beta(alpha, alpha) (1.0 when alpha <= 0; two
+    float64 Gamma(alpha) draws, g0 / (g0 + g1)), then one permutation of the batch, both from
+    `generator` -> (lam as a Python float, perm as a host int64 tensor)."""
+    lam = 1.0
+    if alpha > 0:
+        g = torch._standard_gamma(torch.full((2,), float(alpha), dtype=torch.float64), generator=generator)
+        lam = float(g[0] / (g[0] + g[1]))
+    return lam, torch.randperm(n, generator=generator)
+
+
 class GpuLoader:
     """Iterates a host DataLoader of decoded images and applies the GPU transform. views=2:
     two independent draws of the transform per image as "img1" / "img2" (the two halves of one
-    preprocessing output), "img" an alias of "img1" (the same tensor)."""
+    preprocessing output), "img" an alias of "img1" (the same tensor). mixup_alpha (not None):
+    every batch is mixed after the transform (draw_mix from the transform's generator, after the
+    batch's crop draws; ops.mixup_images): "img" the mixed images, "y_a" (= "label", kept) and
+    "y_b" the two targets, "lam" a Python float."""
 
-    def __init__(self, loader, transform, device, views=1):
+    def __init__(self, loader, transform, device, views=1, mixup_alpha=None):
         if views not in (1, 2):
             raise ValueError(f"views must be 1 or 2, got {views}")
+        if views == 2 and mixup_alpha is not None:
+            raise ValueError("a two-view loader does not mix its batches")
         self.loader, self.transform, self.device, self.views = loader, transform, device, views
+        self.mixup_alpha = None if mixup_alpha is None else float(mixup_alpha)
 
     def __len__(self):
         return len(self.loader)
@@ -163,6 +192,10 @@ class GpuLoader:
             else:
                 out["img"] = self.transform(b["img"])
             out["label"] = b["label"].to(self.device, non_blocking=True)
+            if self.mixup_alpha is not None:
+                lam, perm = draw_mix(self.mixup_alpha, out["img"].shape[0], getattr(self.transform, "generator", None))
+                out["img"], out["y_b"] = ops.mixup_images(out["img"], perm, lam, out["label"])
+                out["y_a"], out["lam"] = out["label"], lam
             yield out
 
 
@@ -184,7 +217,8 @@ class DataManager:
             DataLoader(DatasetWrapper(train, reader), batch_sampler=self.train_batch_sampler, num_workers=nw,
                        collate_fn=_collate, pin_memory=False),
             GpuTransform(cfg, is_train=True, device=self.device, generator=augment_generator(self.replicated)),
-            self.device, views=2 if two_views(cfg) else 1)
+            self.device, views=2 if two_views(cfg) else 1,
+            mixup_alpha=float(cfg.TRAINER.IVLP.get("MIXUP_ALPHA", 1.0)) if mixup(cfg) else None)
 
         def test_loader(data):
             if not data:

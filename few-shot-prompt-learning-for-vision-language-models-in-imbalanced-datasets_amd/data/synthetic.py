@@ -1,7 +1,7 @@
 """Synthetic DataManager with the Dassl surface the trainers read
 (``dm.dataset.classnames``, ``dm.dataset.lab2cname``, ``dm.train_loader_x``,
 ``dm.test_loader``; batches are dicts {"img", "label"}, plus {"img1", "img2"} with
-``two_views``; data_manager.py:55-162,234-263).
+``two_views`` or {"y_a", "y_b", "lam"} with ``mixup_alpha``; data_manager.py:55-162,234-263).
 
 Images are seeded U[0,1) CLIP-normalised tensors, generated once and
 kept resident on the device (no decode/augment in the timed region). Labels follow the
@@ -13,7 +13,9 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .. import ops
 from ..clip import synth
+from .manager import draw_mix
 
 
 class _Dataset:
@@ -24,12 +26,18 @@ class _Dataset:
 
 
 VIEW2_SEED = 500_000  # offset of the second view's image seed from its batch's (two_views)
+MIX_SEED = 700_000  # offset of the mixup stream's seed (mixup_alpha)
 
 
 class SyntheticDataManager:
     def __init__(self, n_cls, resolution, batch_size, n_batches=2, test_batch=100, n_test=0,
-                 per_class_shots=None, device="cuda", seed=1, rank=0, n_test_device=0, two_views=False):
-        """two_views: every training batch also carries "img1" (the same tensor as "img") and
+                 per_class_shots=None, device="cuda", seed=1, rank=0, n_test_device=0, two_views=False,
+                 mixup_alpha=None):
+        """mixup_alpha (not None): every training batch is mixed as data/manager.py GpuLoader mixes
+        them (draw_mix from a generator seeded MIX_SEED + seed + 7919 * rank, one draw per batch in
+        batch order; ops.mixup_images): "img" the mixed images, "y_a" (= "label", kept), "y_b",
+        "lam" (a Python float). Not together with two_views.
+        two_views: every training batch also carries "img1" (the same tensor as "img") and
         "img2", a second set of images drawn from the batch's seed + VIEW2_SEED (the SimCLR
         objectives, data/manager.py two_views; synthetic noise has no augmentation to share, so
         the views are two independent draws).
@@ -37,6 +45,8 @@ class SyntheticDataManager:
         n_test_device: a large test set drawn directly in HBM (torch generator on the
         device; U[0,1) then CLIP-normalised), e.g. the 50,000-image eval timing set of
         SURVEY §8(d) -- 30 GB at 224 px fp32, resident, every image distinct."""
+        if two_views and mixup_alpha is not None:
+            raise ValueError("two_views batches are not mixed")
         self.dataset = _Dataset(synth.synthetic_classnames(n_cls))
         dev = torch.device(device)
         rs = np.random.RandomState(1000 + seed + 7919 * rank)
@@ -45,6 +55,8 @@ class SyntheticDataManager:
         else:
             pool = np.arange(n_cls)
         self.train_loader_x = []
+        mix_gen = torch.Generator()
+        mix_gen.manual_seed(MIX_SEED + seed + 7919 * rank)
         for i in range(n_batches):
             img = synth.make_images(batch_size, resolution, seed=seed + 31 * i + 7919 * rank)
             lab = rs.choice(pool, size=batch_size).astype(np.int64)
@@ -53,6 +65,10 @@ class SyntheticDataManager:
                 img2 = synth.make_images(batch_size, resolution, seed=seed + 31 * i + 7919 * rank + VIEW2_SEED)
                 batch["img1"] = batch["img"]
                 batch["img2"] = torch.from_numpy(img2).to(dev)
+            if mixup_alpha is not None:
+                lam, perm = draw_mix(float(mixup_alpha), batch_size, mix_gen)
+                batch["img"], batch["y_b"] = ops.mixup_images(batch["img"], perm, lam, batch["label"])
+                batch["y_a"], batch["lam"] = batch["label"], lam
             self.train_loader_x.append(batch)
         self.test_loader = []
         for i in range(0, n_test, test_batch):

@@ -153,6 +153,12 @@ def get_cfg_default() -> CfgNode:
                    # ONE encode of the class prompts instead of one per view. Off: the torch
                    # composition and the reference's two forward_once calls, bit for bit as before
                    "FUSED_SIMCLR": False,
+                   # MIXUP: IVLP trains on mixed batches as the reference's default run does
+                   # (TRAINER.IVLP.USE_MIXUP / MIXUP_ALPHA): the training loader mixes every batch
+                   # (clipk_mixup_images; "y_a" / "y_b" / "lam") and the mixed criterion is one native
+                   # call (clipk_ce_loss_mix). Off: no loader mixes (USE_MIXUP alone changes nothing),
+                   # and a batch that carries the mix keys takes the two-call branch as before
+                   "MIXUP": False,
                    # PREFETCH_VISION: CoCoOp starts the next batch's image encoder (frozen) on a side
                    # stream between a step's forward and backward (the loop names the next batch)
                    "PREFETCH_VISION": True,

@@ -436,6 +436,64 @@ def ce_loss_reduce(logits, labels, alpha=None, gamma=2.0, focal=False, grad=True
     return loss, dl
 
 
+def ce_loss_mix(logits, y_a, y_b, lam, alpha=None, gamma=2.0, focal=False, grad=True, reduction="mean"):
+    """clipk_ce_loss_mix: the mixup criterion lam * L(logits, y_a) + (1 - lam) * L(logits, y_b)
+    (L = CE / focal with its mean / sum) -> (loss [], dlogits = d loss / d logits) in one launch."""
+    _need(logits, "logits", torch.float32)
+    _need(y_a, "y_a", torch.int64)
+    _need(y_b, "y_b", torch.int64)
+    if logits.dim() != 2:
+        raise N.ClipkError(f"logits must be [B, C], got {tuple(logits.shape)}")
+    B, C = logits.shape
+    if y_a.shape != (B,) or y_b.shape != (B,):
+        raise N.ClipkError(f"y_a and y_b must be [{B}], got {tuple(y_a.shape)} and {tuple(y_b.shape)}")
+    if alpha is not None:
+        _need(alpha, "alpha", torch.float32)
+        if alpha.numel() < C:
+            raise N.ClipkError(f"alpha must hold {C} class weights, got {alpha.numel()}")
+    red = {"mean": 1, "sum": 2}[reduction]
+    row = torch.empty(2 * B, device=logits.device)
+    loss = torch.empty((), device=logits.device)
+    dl = torch.empty_like(logits) if grad else None
+    N.call("clipk_ce_loss_mix", B, C, _p(logits), _p(y_a), _p(y_b), float(lam), _p(alpha), float(gamma), int(focal),
+           1.0 / B if reduction == "mean" else 1.0, red, _p(row), _p(loss), _p(dl), _stream())
+    return loss, dl
+
+
+def mixup_images(x, perm, lam, labels=None):
+    """mixup_data (independentVL.py:435-449): (lam * x + (1 - lam) * x[perm], labels[perm] or None)
+    for fp32 x [B, ...]. perm: a host integer tensor [B] with entries in [0, B), checked here and
+    uploaded on the current stream without a synchronisation. CUDA x: one clipk_mixup_images launch,
+    bitwise the torch expression; CPU x: the torch expression itself (loader logic off device)."""
+    _need(x, "x", torch.float32, cuda=False)
+    if x.dim() < 1:
+        raise N.ClipkError("x must be [B, ...]")
+    B = x.shape[0]
+    if perm is None or perm.is_cuda or perm.dtype not in (torch.int32, torch.int64):
+        raise N.ClipkError("perm must be a host int32 / int64 tensor")
+    if perm.shape != (B,):
+        raise N.ClipkError(f"perm must be [{B}], got {tuple(perm.shape)}")
+    if B and (int(perm.min()) < 0 or int(perm.max()) >= B):
+        raise N.ClipkError(f"perm entries must lie in [0, {B})")
+    if labels is not None:
+        _need(labels, "labels", torch.int64, cuda=False)
+        if labels.shape != (B,) or labels.device != x.device:
+            raise N.ClipkError(f"labels must be [{B}] on x's device, got {tuple(labels.shape)} on {labels.device}")
+    lam = float(lam)
+    if not x.is_cuda:
+        idx = perm.long()
+        return lam * x + (1 - lam) * x[idx], (labels[idx] if labels is not None else None)
+    out = torch.empty_like(x)
+    y_b = torch.empty_like(labels) if labels is not None else None
+    if B:
+        if not x.numel():  # nothing to mix: the kernel wants n_per >= 1
+            return out, (labels[perm.long().to(x.device)] if labels is not None else None)
+        d_perm = perm.to(torch.int32).to(x.device, non_blocking=True)
+        N.call("clipk_mixup_images", B, x.numel() // B, _p(x), _p(d_perm), _p(labels), _p(y_b), lam, 1.0 - lam,
+               _p(out), _stream())
+    return out, y_b
+
+
 def ntxent_loss(a, b, temperature=0.07, grad=True, grad_scale=1.0):
     """clipk_ntxent_loss: NT-Xent of the two views a, b (fp32 [n, D]) -> (loss [], da, db) with
     da / db = grad_scale * d loss / d a, b (None when not grad). 1 <= n <= 512."""

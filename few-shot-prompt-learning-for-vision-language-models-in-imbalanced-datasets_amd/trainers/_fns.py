@@ -139,6 +139,25 @@ class CrossEntropyFn(torch.autograd.Function):
         return dl, None, None, None, None, None
 
 
+class MixedCrossEntropyFn(torch.autograd.Function):
+    """mixup_criterion (independentVL.py:451-460) on CrossEntropyFn's CE / focal loss:
+    lam * L(logits, y_a) + (1 - lam) * L(logits, y_b) with L's own 'mean' | 'sum', the loss and its
+    gradient from the forward call (clipk_ce_loss_mix)."""
+
+    @staticmethod
+    def forward(ctx, logits, y_a, y_b, lam, alpha, gamma, focal, reduction="mean"):
+        loss, ctx.dl = ops.ce_loss_mix(logits.contiguous(), y_a, y_b, lam, alpha, gamma, focal,
+                                       grad=logits.requires_grad, reduction=reduction)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        # (as CrossEntropyFn.backward: no multiply launch for backward_unit's cached 1.0)
+        if g.data_ptr() == unit_grad(g.device).data_ptr():
+            return ctx.dl, None, None, None, None, None, None, None
+        return ctx.dl * g, None, None, None, None, None, None, None
+
+
 class NTXentFn(torch.autograd.Function):
     """NT-Xent of two views (LogitsNTXentLoss, coop.py:72-123; ImageNTXentLoss, independentVL.py:
     73-112), loss and both views' gradients from the forward call (clipk_ntxent_loss)."""

@@ -28,7 +28,7 @@ from ..engine.trainer import TrainerX, load_clip
 from ..engine.optim import build_optimizer, build_lr_scheduler
 from ..engine.metrics import LossSummary
 from ..clip.model import TextEncodeFn, DeepTextEncodeFn, PromptedVisionFn
-from ._fns import PromptAssembleFn, CrossEntropyFn, NTXentFn, ntxent_fused_ok
+from ._fns import PromptAssembleFn, CrossEntropyFn, MixedCrossEntropyFn, NTXentFn, ntxent_fused_ok
 from .losses import focal_alpha
 from .prompt_base import init_prompts, grads_finite
 
@@ -176,9 +176,17 @@ class IVLPCustomCLIP(_DeepCLIP):
             if alpha is not None else None
         self.simclr_alpha = float(sec.get("SIMCLR_ALPHA", 0.0))
         self.fused_simclr = bool(cfg.get("NATIVE", {}).get("FUSED_SIMCLR", False))
+        self.native_mixup = bool(cfg.get("NATIVE", {}).get("MIXUP", False))
 
     def criterion(self, logits, y):
         return CrossEntropyFn.apply(logits, y, self.alpha, 2.0, self.focal)
+
+    def mixed_criterion(self, logits, y_a, y_b, lam):
+        """mixup_criterion (independentVL.py:451-460). NATIVE.MIXUP: one clipk_ce_loss_mix call;
+        off: the two criterion calls combined through autograd, as before."""
+        if self.native_mixup:
+            return MixedCrossEntropyFn.apply(logits, y_a, y_b, lam, self.alpha, 2.0, self.focal)
+        return lam * self.criterion(logits, y_a) + (1 - lam) * self.criterion(logits, y_b)
 
     def forward(self, image1, label=None, image2=None):
         img, _, logits = self.features(image1)
@@ -278,7 +286,9 @@ class _DeepTrainer(TrainerX):
 @TRAINER_REGISTRY.register()
 class IVLP(_DeepTrainer):
     """independentVL.py:337-589. Batches: {"img", "label"}; SimCLR {"img1", "img2", "label"};
-    mixup {"img", "y_a", "y_b", "lam"} (parse_batch_train, independentVL.py:435-460). USE_KD
+    mixup {"img", "y_a", "y_b", "lam"} (parse_batch_train, independentVL.py:435-460; the loaders
+    yield them with USE_MIXUP and NATIVE.MIXUP, data/manager.py mixup, and the mixed criterion is
+    then one clipk_ce_loss_mix call). USE_KD
     needs a pretrained timm teacher (independentVL.py:360-365) and is refused."""
 
     SEC, MODEL_NAME = "IVLP", "VLPromptLearner"
@@ -306,7 +316,7 @@ class IVLP(_DeepTrainer):
         if mix is not None:
             y_a, y_b, lam = mix
             _, _, logits = m.features(image1)
-            loss = lam * m.criterion(logits, y_a) + (1 - lam) * m.criterion(logits, y_b)
+            loss = m.mixed_criterion(logits, y_a, y_b, lam)
         else:
             loss = m(image1, label, image2)
         self._step(loss, batch, image1.shape[0])

@@ -23,6 +23,8 @@
  *                         (coop.py:356-363, cocoop.py:238-251)
  *   clipk_ce_loss         nn.CrossEntropyLoss / MultiClassFocalLoss fwd+bwd
  *                         (coop.py:131-163,324; cocoop.py:66-101,233)
+ *   clipk_mixup_images    mixup_data: lam * x + (1 - lam) * x[perm] (independentVL.py:435-449)
+ *   clipk_ce_loss_mix     mixup_criterion on CE / focal fwd+bwd (independentVL.py:451-460)
  *   clipk_ntxent_loss     LogitsNTXentLoss / ImageNTXentLoss fwd+bwd
  *                         (coop.py:72-123; independentVL.py:73-112)
  *   clipk_meta_net_*      CoCoOp Meta-Net Linear-ReLU-Linear (cocoop.py:139-143,182-185)
@@ -381,6 +383,36 @@ int clipk_ce_loss(int B, int C, const float* logits, const int64_t* labels, cons
 int clipk_ce_loss_reduce(int B, int C, const float* logits, const int64_t* labels, const float* alpha,
                          float gamma, int focal, float grad_scale, int reduction, float* row_loss,
                          float* loss, float* dlogits, void* stream);
+
+/* Mixup (mixup_data / mixup_criterion, independentVL.py:435-460; csrc/mixup.hip).
+ *
+ * clipk_mixup_images: out[b, i] = w0 * x[b, i] + w1 * x[p, i], p = perm[b], for fp32 x / out
+ * [B, n_per] (contiguous) and a device array perm [B]. With labels and y_b (int64 [B], both or
+ * neither) the same launch writes y_b[b] = labels[p]. A perm entry outside [0, B) is never
+ * dereferenced: that row takes p = b. The two products are rounded to fp32 separately and then
+ * added (no FMA contraction): with w0 = (float)lam and w1 = (float)(1.0 - lam) formed in double on
+ * the host the result is torch's lam * x + (1 - lam) * x[perm] bit for bit. 16-byte accesses when
+ * n_per % 4 == 0 and x / out are 16-byte aligned, one float at a time otherwise. B == 0: CLIPK_OK,
+ * nothing launched. CLIPK_ESHAPE: B < 0 or n_per <= 0. CLIPK_EINVAL: x, perm or out null, only
+ * one of labels / y_b given, or out overlapping x (rows are read while others are written). */
+int clipk_mixup_images(int B, long n_per, const float* x, const int* perm, const int64_t* labels,
+                       int64_t* y_b, float w0, float w1, float* out, void* stream);
+
+/* clipk_ce_loss_reduce for a mixed batch: one launch, one max and one sum-of-exponentials pass per
+ * row shared by the two targets y_a, y_b (int64 [B]). With L the CE / focal row loss of
+ * clipk_ce_loss (the same arithmetic) and red = the mean (the sum in row order times 1 / B,
+ * reduction 1) or the sum (reduction 2):
+ *   row_loss [2B] = L(logits, y_a) then L(logits, y_b),
+ *   loss[0] = lam * red(row_loss[:B]) + (1 - lam) * red(row_loss[B:]),
+ *   dlogits[b, c] = grad_scale * (lam * w_a (p_c - [c == y_a]) + (1 - lam) * w_b (p_c - [c == y_b]))
+ * with p = softmax(logits[b]) and w_a, w_b = 1 (CE) or the focal weight of the row's target; a row
+ * with y_a == y_b gets both terms on one column. dlogits NULL: forward only. A label outside
+ * [0, C) is not dereferenced: that row's loss (and gradient) is NaN. No atomics, fixed summation
+ * order: bitwise reproducible. Error codes as clipk_ce_loss_reduce (CLIPK_EINVAL: logits, y_a,
+ * y_b, row_loss or loss null, reduction not 1 / 2; CLIPK_ESHAPE: B <= 0 or C <= 0). */
+int clipk_ce_loss_mix(int B, int C, const float* logits, const int64_t* y_a, const int64_t* y_b,
+                      float lam, const float* alpha, float gamma, int focal, float grad_scale,
+                      int reduction, float* row_loss, float* loss, float* dlogits, void* stream);
 
 /* NT-Xent (SimCLR) loss of two views a, b (fp32 [n, D], contiguous), forward and gradient:
  * LogitsNTXentLoss on the two views' logits (coop.py:72-123) and ImageNTXentLoss on their image
