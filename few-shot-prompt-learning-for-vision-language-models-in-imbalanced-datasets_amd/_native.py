@@ -103,6 +103,9 @@ SIGNATURES = {
     "clipk_mixup_images": (_I, [_I, _L, _P, _P, _P, _P, _F, _F, _P, _P]),
     "clipk_ntxent_ws_bytes": (_S, [_I, _I]),
     "clipk_ntxent_loss": (_I, [_I, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "clipk_src_head_ws_bytes": (_S, [_I, _I, _I]),
+    "clipk_src_head": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P,
+                            _P]),
     "clipk_meta_net_fwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "clipk_meta_net_fwd_norm": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "clipk_status_take": (_I, [_P, _P, _P]),

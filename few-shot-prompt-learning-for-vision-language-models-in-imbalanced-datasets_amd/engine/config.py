@@ -126,7 +126,9 @@ def get_cfg_default() -> CfgNode:
             "MAPLE": {"N_CTX": 2, "CTX_INIT": "a photo of a", "PREC": "fp16", "PROMPT_DEPTH": 9,
                       "USE_FOCAL_LOSS": False},
             # PromptSRC/train.py:125-141 (+ LOGITS_LOSS_WEIGHT and USE_GPA, which the trainer
-            # reads, promptsrc.py:320, 330, but train.py never defines)
+            # reads, promptsrc.py:320, 330, but train.py never defines). LOSS_TYPE "ce" | "focal":
+            # the meaning the key has in COOP (focal: class-frequency alpha from PER_CLASS_SHOTS,
+            # gamma 2); LABEL_SCOPE and SIMCLR_ALPHA are carried and not read
             "PROMPTSRC": {"N_CTX_VISION": 4, "N_CTX_TEXT": 4, "CTX_INIT": "a photo of a", "PREC": "fp16",
                           "PROMPT_DEPTH_VISION": 9, "PROMPT_DEPTH_TEXT": 9, "TEXT_LOSS_WEIGHT": 25,
                           "IMAGE_LOSS_WEIGHT": 10, "LOGITS_LOSS_WEIGHT": 1.0, "GPA_MEAN": 15, "GPA_STD": 1,
@@ -159,6 +161,12 @@ def get_cfg_default() -> CfgNode:
                    # call (clipk_ce_loss_mix). Off: no loader mixes (USE_MIXUP alone changes nothing),
                    # and a batch that carries the mix keys takes the two-call branch as before
                    "MIXUP": False,
+                   # FUSED_SRC: PromptSRC's head -- the feature normalisations, both logit products,
+                   # CE / focal, the two L1 terms, the KL term, their weights and all of their
+                   # backward -- as one native call on the raw encoder outputs (clipk_src_head), where
+                   # it takes the inputs (CUDA fp32, batch <= 128). Off: the torch composition with
+                   # autograd, bit for bit as before
+                   "FUSED_SRC": False,
                    # PREFETCH_VISION: CoCoOp starts the next batch's image encoder (frozen) on a side
                    # stream between a step's forward and backward (the loop names the next batch)
                    "PREFETCH_VISION": True,

@@ -517,6 +517,53 @@ def ntxent_loss(a, b, temperature=0.07, grad=True, grad_scale=1.0):
     return loss, da, db
 
 
+SRC_HEAD_MAX_B = 128  # clipk_src_head's batch ceiling
+
+
+def src_head(img, txt, zs_img, fixed_n, fixed_q, labels, alpha, gamma, focal, scale, w_text, w_image, w_logits,
+             grad=True, grad_scale=1.0, want_logits=False):
+    """clipk_src_head: the PromptSRC objective on the raw prompted image [B, E] / text [C, E] features,
+    the raw frozen image features zs_img [B, E] and the frozen normalised text features fixed_n /
+    fixed_q [C, E] (fixed_q: the fp16-valued copy of the zero-shot logits) -> (loss [5] = total, ce,
+    kl, l1_text, l1_image; logits [B, C] or None; d_img, d_txt = grad_scale * d total / d img, txt,
+    None when not grad). 1 <= B <= 128."""
+    for t, name in ((img, "img"), (txt, "txt"), (zs_img, "zs_img"), (fixed_n, "fixed_n"), (fixed_q, "fixed_q")):
+        _need(t, name, torch.float32)
+        if t.dim() != 2:
+            raise N.ClipkError(f"{name} must be 2-D, got {tuple(t.shape)}")
+    _need(labels, "labels", torch.int64)
+    B, E = img.shape
+    C = txt.shape[0]
+    if zs_img.shape != (B, E) or txt.shape != (C, E) or fixed_n.shape != (C, E) or fixed_q.shape != (C, E):
+        raise N.ClipkError(f"src_head needs img, zs_img [B, E] and txt, fixed_n, fixed_q [C, E], got "
+                           f"{[tuple(t.shape) for t in (img, zs_img, txt, fixed_n, fixed_q)]}")
+    if labels.shape != (B,):
+        raise N.ClipkError(f"labels must be [{B}], got {tuple(labels.shape)}")
+    if not 1 <= B <= SRC_HEAD_MAX_B or C < 1 or E < 1:
+        raise N.ClipkError(f"src_head needs 1 <= B <= {SRC_HEAD_MAX_B}, C >= 1 and E >= 1, got B = {B}, C = {C}, "
+                           f"E = {E}")
+    if alpha is not None:
+        _need(alpha, "alpha", torch.float32)
+        if alpha.numel() < C:
+            raise N.ClipkError(f"alpha must hold {C} class weights, got {alpha.numel()}")
+    if any(t.device != img.device for t in (txt, zs_img, fixed_n, fixed_q, labels) + ((alpha,) if alpha is not None
+                                                                                      else ())):
+        raise N.ClipkError("src_head: every tensor must be on one device")
+    if not scale > 0:
+        raise N.ClipkError(f"scale must be positive, got {scale}")
+    if focal and not gamma >= 0:
+        raise N.ClipkError(f"focal needs gamma >= 0, got {gamma}")
+    ws = torch.empty(N.load().clipk_src_head_ws_bytes(B, C, E), dtype=torch.uint8, device=img.device)
+    loss = torch.empty(5, device=img.device)
+    logits = torch.empty(B, C, device=img.device) if want_logits else None
+    d_img = torch.empty_like(img) if grad else None
+    d_txt = torch.empty_like(txt) if grad else None
+    N.call("clipk_src_head", B, C, E, _p(img), _p(txt), _p(zs_img), _p(fixed_n), _p(fixed_q), _p(labels), _p(alpha),
+           float(gamma), int(bool(focal)), float(scale), float(w_text), float(w_image), float(w_logits),
+           float(grad_scale), _p(loss), _p(logits), _p(d_img), _p(d_txt), _p(ws), _stream())
+    return loss, logits, d_img, d_txt
+
+
 def status_take(flags, host_word):
     """clipk_status_take: flags -> host_word (pinned int32), flags cleared (stream-ordered)."""
     N.call("clipk_status_take", _p(flags), _p(host_word), _stream())

@@ -182,6 +182,45 @@ def ntxent_fused_ok(a, b):
             and a.dim() == 2 and a.shape == b.shape and 1 <= a.shape[0] <= 512 and a.shape[1] >= 1)
 
 
+class SRCHeadFn(torch.autograd.Function):
+    """The PromptSRC objective (promptsrc.py:171-213, 296-323) on the raw prompted image / text
+    features: the total loss and both of its gradients from the forward call (clipk_src_head).
+    out (a dict, optional) receives "parts" = the call's loss [5] (total, ce, kl, l1_text, l1_image;
+    detached) and, when it holds a true "want_logits", "logits" [B, C]."""
+
+    @staticmethod
+    def forward(ctx, img, txt, zs_img, fixed_n, fixed_q, labels, alpha, gamma, focal, scale, w_text, w_image,
+                w_logits, out=None):
+        grad = img.requires_grad or txt.requires_grad
+        want_logits = bool(out is not None and out.get("want_logits"))
+        loss, logits, ctx.d_img, ctx.d_txt = ops.src_head(
+            img.contiguous(), txt.contiguous(), zs_img.contiguous(), fixed_n, fixed_q, labels, alpha, gamma, focal,
+            scale, w_text, w_image, w_logits, grad=grad, want_logits=want_logits)
+        if out is not None:
+            out["parts"], out["logits"] = loss, logits
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        none = (None,) * 12
+        # (as CrossEntropyFn.backward: no multiply launch for backward_unit's cached 1.0)
+        if g.data_ptr() == unit_grad(g.device).data_ptr():
+            return (ctx.d_img, ctx.d_txt) + none
+        return (ctx.d_img * g, ctx.d_txt * g) + none
+
+
+def src_head_fused_ok(img, txt, zs_img, fixed_n, fixed_q):
+    """The shapes and types clipk_src_head takes: CUDA fp32 contiguous img, zs_img [B, E] and txt,
+    fixed_n, fixed_q [C, E], 1 <= B <= 128."""
+    ts = (img, txt, zs_img, fixed_n, fixed_q)
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() for t in ts):
+        return False
+    B, E = img.shape
+    C = txt.shape[0]
+    return (zs_img.shape == (B, E) and txt.shape == (C, E) and fixed_n.shape == (C, E) and fixed_q.shape == (C, E)
+            and 1 <= B <= ops.SRC_HEAD_MAX_B and C >= 1 and E >= 1)
+
+
 _UNIT = {}
 
 

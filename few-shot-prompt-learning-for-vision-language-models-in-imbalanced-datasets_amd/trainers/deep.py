@@ -10,7 +10,8 @@ ViT (PromptedVisionFn: n_vpt prompt rows after the image tokens, replaced again 
 1..depth-1, model.py:234-241, 299-312, 413-420, 465-472), whose input-grad backward reaches
 every visual prompt. Prompt tokens are rounded to fp16 values as the reference's ``.half()``
 does (gradient passed straight through). The [B, C] cosine head and the losses on it are
-composed from torch ops on a few KB (the image side needs its gradient here).
+composed from torch ops on a few KB (the image side needs its gradient here); PromptSRC's
+whole objective is one native call instead under NATIVE.FUSED_SRC (clipk_src_head).
 """
 from __future__ import annotations
 
@@ -28,7 +29,9 @@ from ..engine.trainer import TrainerX, load_clip
 from ..engine.optim import build_optimizer, build_lr_scheduler
 from ..engine.metrics import LossSummary
 from ..clip.model import TextEncodeFn, DeepTextEncodeFn, PromptedVisionFn
-from ._fns import PromptAssembleFn, CrossEntropyFn, MixedCrossEntropyFn, NTXentFn, ntxent_fused_ok
+from .. import ops
+from ._fns import (PromptAssembleFn, CrossEntropyFn, MixedCrossEntropyFn, NTXentFn, ntxent_fused_ok, SRCHeadFn,
+                   src_head_fused_ok)
 from .losses import focal_alpha
 from .prompt_base import init_prompts, grads_finite
 
@@ -442,6 +445,19 @@ class PromptSRCCustomCLIP(_DeepCLIP):
         self.prompt_learner.fixed_embeddings = encode_prompts(
             clip_model, ["a photo of a {}.".format(n.replace("_", " ")) for n in classnames],
             clip_model.logit_scale.device)
+        # LOSS_TYPE "ce" | "focal", the meaning the key has in TRAINER.COOP (trainers/coop.py here)
+        self.loss_type = sec.get("LOSS_TYPE", "ce")
+        self.alpha, self.gamma, self.focal = None, 0.0, False
+        if self.loss_type == "focal":
+            print(">> Use Focal Loss!")
+            alpha = focal_alpha(cfg.DATASET.get("PER_CLASS_SHOTS", None), self.n_cls, zero_guard=True)
+            if alpha is not None:
+                self.alpha = torch.tensor(alpha, dtype=torch.float32, device=clip_model.logit_scale.device)
+            self.gamma, self.focal = 2.0, True
+        elif self.loss_type != "ce":
+            raise ValueError(f"Unknown loss_type = {self.loss_type}")
+        self.fused_src = bool(cfg.get("NATIVE", {}).get("FUSED_SRC", False))
+        self._fixed_nq = None
 
     def forward(self, image, label=None):
         img, txt, logits = self.features(image)
@@ -451,7 +467,28 @@ class PromptSRCCustomCLIP(_DeepCLIP):
         with torch.no_grad():
             zs = F.normalize(self.clip.visual(image), dim=-1)
             zs_logits = self.logit_scale_value * zs @ fixed.half().float().t()
-        return CrossEntropyFn.apply(logits, label, None, 0.0, False), txt, fixed, zs, img, zs_logits, logits
+        return (CrossEntropyFn.apply(logits, label, self.alpha, self.gamma, self.focal), txt, fixed, zs, img,
+                zs_logits, logits)
+
+    def fused_loss(self, image, label, w_text, w_image, w_logits, out=None):
+        """NATIVE.FUSED_SRC: the step's whole objective as one SRCHeadFn call (clipk_src_head) on the
+        raw encoder outputs. None where the call does not take the inputs (the caller then runs
+        forward() and the torch composition). out: SRCHeadFn's dict for the loss parts / logits."""
+        if not (image.is_cuda and 1 <= image.shape[0] <= ops.SRC_HEAD_MAX_B):
+            return None
+        if self._fixed_nq is None:  # constants of the model, formed once (not state-dict entries)
+            with torch.no_grad():
+                fixed = F.normalize(self.prompt_learner.fixed_embeddings.float(), dim=-1).contiguous()
+                self._fixed_nq = (fixed, fixed.half().float())
+        fixed_n, fixed_q = self._fixed_nq
+        txt = self.text_features().float().contiguous()
+        img = self.image_features(image).float().contiguous()
+        with torch.no_grad():
+            zs = self.clip.visual(image).float().contiguous()
+        if not src_head_fused_ok(img, txt, zs, fixed_n, fixed_q):
+            return None
+        return SRCHeadFn.apply(img, txt, zs, fixed_n, fixed_q, label, self.alpha, self.gamma, self.focal,
+                               self.logit_scale_value, w_text, w_image, w_logits, out)
 
 
 @TRAINER_REGISTRY.register()
@@ -480,12 +517,17 @@ class PromptSRC(_DeepTrainer):
     def forward_backward(self, batch):
         image, label = self.parse_batch_train(batch)
         s = self.sec
-        loss_ce, txt, fixed, zs, img, zs_logits, logits = self.model(image, label)
-        l_text = F.l1_loss(txt, fixed, reduction="mean") * s.TEXT_LOSS_WEIGHT
-        l_img = F.l1_loss(img, zs, reduction="mean") * s.IMAGE_LOSS_WEIGHT
-        l_logits = F.kl_div(F.log_softmax(logits, dim=1), F.log_softmax(zs_logits, dim=1), reduction="sum",
-                            log_target=True) / logits.numel() * s.get("LOGITS_LOSS_WEIGHT", 1.0)
-        loss = loss_ce + (l_logits + l_text + l_img)
+        loss = None
+        if self.model.fused_src:
+            loss = self.model.fused_loss(image, label, s.TEXT_LOSS_WEIGHT, s.IMAGE_LOSS_WEIGHT,
+                                         s.get("LOGITS_LOSS_WEIGHT", 1.0))
+        if loss is None:
+            loss_ce, txt, fixed, zs, img, zs_logits, logits = self.model(image, label)
+            l_text = F.l1_loss(txt, fixed, reduction="mean") * s.TEXT_LOSS_WEIGHT
+            l_img = F.l1_loss(img, zs, reduction="mean") * s.IMAGE_LOSS_WEIGHT
+            l_logits = F.kl_div(F.log_softmax(logits, dim=1), F.log_softmax(zs_logits, dim=1), reduction="sum",
+                                log_target=True) / logits.numel() * s.get("LOGITS_LOSS_WEIGHT", 1.0)
+            loss = loss_ce + (l_logits + l_text + l_img)
         self._step(loss, batch, image.shape[0])
         out = LossSummary()
         out["loss"] = loss

@@ -27,6 +27,8 @@
  *   clipk_ce_loss_mix     mixup_criterion on CE / focal fwd+bwd (independentVL.py:451-460)
  *   clipk_ntxent_loss     LogitsNTXentLoss / ImageNTXentLoss fwd+bwd
  *                         (coop.py:72-123; independentVL.py:73-112)
+ *   clipk_src_head        PromptSRC's normalisations, logits, CE / focal + L1 + KL objective
+ *                         fwd+bwd (promptsrc.py:171-213, 296-323)
  *   clipk_meta_net_*      CoCoOp Meta-Net Linear-ReLU-Linear (cocoop.py:139-143,182-185)
  *   clipk_sgd_step        torch.optim.SGD momentum/wd step (dassl optim/optimizer.py:105-113)
  *   clipk_sgd_step_multi  the same over a param group's tensors in one launch
@@ -429,6 +431,37 @@ size_t clipk_ntxent_ws_bytes(int n, int D);
 int clipk_ntxent_loss(int n, int D, const float* a, const float* b, float temperature,
                       float grad_scale, float* loss, float* da, float* db,
                       void* ws, void* stream);
+
+/* PromptSRC head (promptsrc.py:171-213, 296-323; csrc/srchead.hip): the whole objective and its
+ * gradients with respect to the raw (un-normalised) prompted features, all fp32 and contiguous.
+ * With n(x) = x / max(|x|, 1e-12) (F.normalize), u_b = n(img_b), t_c = n(txt_c), z_b = n(zs_img_b),
+ * s = scale u t^T, q = scale z fixed_q^T and ls, lq the row log-softmaxes of s and q:
+ *   ce       = mean_b L(s_b, labels_b), L the CE / focal row loss of clipk_ce_loss (alpha, gamma,
+ *              focal: the same arithmetic),
+ *   kl       = w_logits / (B C) sum_{b,c} exp(lq) (lq - ls),
+ *   l1_text  = w_text / (C E) sum |t - fixed_n|,     l1_image = w_image / (B E) sum |u - z|,
+ *   loss[0..4] = total (the sum of the four), ce, kl, l1_text, l1_image.
+ * fixed_n: the frozen text features, L2-normalised; fixed_q: the copy the zero-shot logits use
+ * (fixed_n rounded to fp16 values, promptsrc.py:204). logits [B,C] (optional): s.
+ * With G = d total / d s = (CE / focal gradient) + w_logits / (B C) (softmax(s) - softmax(q)),
+ *   g_u = scale G t + w_image / (B E) sign(u - z),  g_t = scale G^T u + w_text / (C E) sign(t - fixed_n)
+ * (sign(0) = 0) and d x = (g - (g . n) n) / |x| through the normalisation,
+ *   d_img [B,E], d_txt [C,E] = grad_scale * d total / d img, txt;
+ * both NULL: forward only, no gradient work is launched. fp32 products and sums throughout (no
+ * MFMA), each log-sum-exp kept as (row max, log of the sum), every sum in a fixed order (bitwise
+ * reproducible, no atomics); 4 launches with gradients, 3 without. C = 1 gives ce == 0 and kl == 0
+ * exactly. A label outside [0, C) is never dereferenced: ce (and the total, and that row's
+ * gradient) is NaN.
+ * ws: caller workspace of clipk_src_head_ws_bytes(B, C, E) bytes (0 for a shape out of range); no
+ * allocation or synchronisation inside. Any C >= 1 and E >= 1, 1 <= B <= 128 (else CLIPK_ESHAPE).
+ * CLIPK_EINVAL: img, txt, zs_img, fixed_n, fixed_q, labels, loss or ws null, only one of d_img /
+ * d_txt given, scale <= 0, focal with gamma < 0. */
+size_t clipk_src_head_ws_bytes(int B, int C, int E);
+int clipk_src_head(int B, int C, int E, const float* img, const float* txt, const float* zs_img,
+                   const float* fixed_n, const float* fixed_q, const int64_t* labels,
+                   const float* alpha, float gamma, int focal, float scale, float w_text,
+                   float w_image, float w_logits, float grad_scale, float* loss, float* logits,
+                   float* d_img, float* d_txt, void* ws, void* stream);
 
 /* CoCoOp Meta-Net: h = relu(x W1^T + b1); y = h W2^T + b2. x [B,V], W1 [Hd,V], W2 [Wd,Hd].
  * The CLIP widths (V % 256 == 0, V <= 1024, Hd <= 64, x / W1 16-B aligned) take the
