@@ -106,6 +106,8 @@ SIGNATURES = {
     "clipk_src_head_ws_bytes": (_S, [_I, _I, _I]),
     "clipk_src_head": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P,
                             _P]),
+    "clipk_probe_head_ws_bytes": (_S, [_I, _I, _I]),
+    "clipk_probe_head": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _F, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
     "clipk_meta_net_fwd": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "clipk_meta_net_fwd_norm": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "clipk_status_take": (_I, [_P, _P, _P]),

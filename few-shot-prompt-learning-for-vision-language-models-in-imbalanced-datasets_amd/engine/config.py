@@ -139,6 +139,15 @@ def get_cfg_default() -> CfgNode:
                      "PROMPT_DEPTH_VISION": 9, "PROMPT_DEPTH_TEXT": 9, "USE_FOCAL_LOSS": False,
                      "SIMCLR_ALPHA": 0.0, "USE_MIXUP": True, "MIXUP_ALPHA": 1.0, "USE_KD": False,
                      "KD_TEACHER_MODEL": "resnet50", "KD_ALPHA": 1.0, "KD_T": 4.0},
+            # LinearProbeCLIP (trainers/linear_probe.py; the fork's own keys are not known, these are
+            # this package's definition): a Linear(E, C) on the frozen image features. LOSS_TYPE
+            # "ce" | "focal" as in COOP; INIT "zeroshot" (the class prompts' text features) |
+            # "zeros"; LOGIT_SCALE 0: CLIP's own logit scale; CACHE_FEATURES: the encoder runs in
+            # epoch 0 only, later epochs train on the stored features (CACHE_SHUFFLE: reshuffled
+            # every epoch; off: the stored batches replayed)
+            "LINEAR_PROBE": {"PREC": "fp16", "LOSS_TYPE": "ce", "NORMALIZE": True, "BIAS": True,
+                             "INIT": "zeroshot", "LOGIT_SCALE": 0.0, "CACHE_FEATURES": False,
+                             "CACHE_SHUFFLE": True},
         },
         # MI355X-native knobs (not in the reference): prompt truncation to the EOT and the
         # max rows per text-encoder launch chunk (memory bound for large B*C).
@@ -167,6 +176,12 @@ def get_cfg_default() -> CfgNode:
                    # it takes the inputs (CUDA fp32, batch <= 128). Off: the torch composition with
                    # autograd, bit for bit as before
                    "FUSED_SRC": False,
+                   # FUSED_PROBE: LinearProbeCLIP's head -- the feature normalisation, the Linear, CE /
+                   # focal and the gradients of weight and bias -- as one native call on the image
+                   # features (clipk_probe_head), and inference as its scoring-only form, where it
+                   # takes the inputs (CUDA fp32, batch <= 512). Off: the torch composition with
+                   # autograd
+                   "FUSED_PROBE": False,
                    # PREFETCH_VISION: CoCoOp starts the next batch's image encoder (frozen) on a side
                    # stream between a step's forward and backward (the loop names the next batch)
                    "PREFETCH_VISION": True,

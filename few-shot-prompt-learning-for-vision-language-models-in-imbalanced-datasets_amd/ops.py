@@ -564,6 +564,67 @@ def src_head(img, txt, zs_img, fixed_n, fixed_q, labels, alpha, gamma, focal, sc
     return loss, logits, d_img, d_txt
 
 
+PROBE_HEAD_MAX_B = 512  # clipk_probe_head's batch ceiling
+
+
+def probe_head(feat, w, bias, labels, alpha, gamma, focal, normalize, scale, grad=True, want_logits=False,
+               grad_scale=1.0):
+    """clipk_probe_head: the linear probe's head on frozen image features feat [B, E] with the
+    classifier w [C, E], bias [C] or None -> (loss [], logits [B, C] or None, d_w, d_bias =
+    grad_scale * d loss / d w, bias; None when not grad, d_bias None without a bias).
+    logits = scale * u w^T + bias with u = F.normalize(feat) when normalize, feat otherwise; loss =
+    the mean CE / focal of clipk_ce_loss. labels None: scoring only -> (None, logits, None, None).
+    1 <= B <= 512."""
+    for t, name in ((feat, "feat"), (w, "w")):
+        _need(t, name, torch.float32)
+        if t.dim() != 2:
+            raise N.ClipkError(f"{name} must be 2-D, got {tuple(t.shape)}")
+    B, E = feat.shape
+    C = w.shape[0]
+    if w.shape != (C, E):
+        raise N.ClipkError(f"probe_head needs feat [B, E] and w [C, E], got {tuple(feat.shape)} and {tuple(w.shape)}")
+    if not 1 <= B <= PROBE_HEAD_MAX_B or C < 1 or E < 1:
+        raise N.ClipkError(f"probe_head needs 1 <= B <= {PROBE_HEAD_MAX_B}, C >= 1 and E >= 1, got B = {B}, "
+                           f"C = {C}, E = {E}")
+    others = []
+    if bias is not None:
+        _need(bias, "bias", torch.float32)
+        if bias.shape != (C,):
+            raise N.ClipkError(f"bias must be [{C}], got {tuple(bias.shape)}")
+        others.append(bias)
+    if labels is not None:
+        _need(labels, "labels", torch.int64)
+        if labels.shape != (B,):
+            raise N.ClipkError(f"labels must be [{B}], got {tuple(labels.shape)}")
+        others.append(labels)
+    if alpha is not None:
+        _need(alpha, "alpha", torch.float32)
+        if alpha.numel() < C:
+            raise N.ClipkError(f"alpha must hold {C} class weights, got {alpha.numel()}")
+        others.append(alpha)
+    if w.device != feat.device or any(t.device != feat.device for t in others):
+        raise N.ClipkError("probe_head: every tensor must be on one device")
+    if not scale > 0:
+        raise N.ClipkError(f"scale must be positive, got {scale}")
+    if focal and not gamma >= 0:
+        raise N.ClipkError(f"focal needs gamma >= 0, got {gamma}")
+    dev = feat.device
+    if labels is None:  # scoring only: one launch, no workspace
+        logits = torch.empty(B, C, device=dev)
+        N.call("clipk_probe_head", B, C, E, _p(feat), _p(w), _p(bias), None, None, 0.0, 0, int(bool(normalize)),
+               float(scale), 1.0, None, _p(logits), None, None, None, _stream())
+        return None, logits, None, None
+    ws = torch.empty(N.load().clipk_probe_head_ws_bytes(B, C, E), dtype=torch.uint8, device=dev)
+    loss = torch.empty((), device=dev)
+    logits = torch.empty(B, C, device=dev) if want_logits else None
+    d_w = torch.empty_like(w) if grad else None
+    d_bias = torch.empty_like(bias) if grad and bias is not None else None
+    N.call("clipk_probe_head", B, C, E, _p(feat), _p(w), _p(bias), _p(labels), _p(alpha), float(gamma),
+           int(bool(focal)), int(bool(normalize)), float(scale), float(grad_scale), _p(loss), _p(logits), _p(d_w),
+           _p(d_bias), _p(ws), _stream())
+    return loss, logits, d_w, d_bias
+
+
 def status_take(flags, host_word):
     """clipk_status_take: flags -> host_word (pinned int32), flags cleared (stream-ordered)."""
     N.call("clipk_status_take", _p(flags), _p(host_word), _stream())

@@ -221,6 +221,46 @@ def src_head_fused_ok(img, txt, zs_img, fixed_n, fixed_q):
             and 1 <= B <= ops.SRC_HEAD_MAX_B and C >= 1 and E >= 1)
 
 
+class ProbeHeadFn(torch.autograd.Function):
+    """The linear probe's head on frozen image features (clipk_probe_head): normalisation, scale *
+    u w^T + bias and the mean CE / focal loss, with the gradients of w and bias from the forward call.
+    feat carries no gradient (the encoder is frozen). out (a dict, optional) receives "logits"
+    [B, C] when it holds a true "want_logits"."""
+
+    @staticmethod
+    def forward(ctx, feat, w, bias, labels, alpha, gamma, focal, normalize, scale, out=None):
+        grad = w.requires_grad or (bias is not None and bias.requires_grad)
+        want_logits = bool(out is not None and out.get("want_logits"))
+        loss, logits, ctx.d_w, ctx.d_bias = ops.probe_head(
+            feat.contiguous(), w.contiguous(), None if bias is None else bias.contiguous(), labels, alpha, gamma,
+            focal, normalize, scale, grad=grad, want_logits=want_logits)
+        if out is not None:
+            out["logits"] = logits
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        none = (None,) * 7
+        # (as CrossEntropyFn.backward: no multiply launch for backward_unit's cached 1.0)
+        if g.data_ptr() == unit_grad(g.device).data_ptr():
+            return (None, ctx.d_w, ctx.d_bias) + none
+        return (None, ctx.d_w * g, None if ctx.d_bias is None else ctx.d_bias * g) + none
+
+
+def probe_head_fused_ok(feat, w, bias):
+    """The shapes and types clipk_probe_head takes: CUDA fp32 contiguous feat [B, E], w [C, E] and
+    bias [C] or None, 1 <= B <= 512."""
+    ts = (feat, w) + ((bias,) if bias is not None else ())
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts):
+        return False
+    if feat.dim() != 2 or w.dim() != 2:
+        return False
+    B, E = feat.shape
+    C = w.shape[0]
+    return (w.shape == (C, E) and (bias is None or bias.shape == (C,))
+            and 1 <= B <= ops.PROBE_HEAD_MAX_B and C >= 1 and E >= 1)
+
+
 _UNIT = {}
 
 

@@ -29,6 +29,8 @@
  *                         (coop.py:72-123; independentVL.py:73-112)
  *   clipk_src_head        PromptSRC's normalisations, logits, CE / focal + L1 + KL objective
  *                         fwd+bwd (promptsrc.py:171-213, 296-323)
+ *   clipk_probe_head      the linear probe's nn.Linear head on frozen image features plus
+ *                         CE / focal, fwd+bwd (this package's LinearProbeCLIP)
  *   clipk_meta_net_*      CoCoOp Meta-Net Linear-ReLU-Linear (cocoop.py:139-143,182-185)
  *   clipk_sgd_step        torch.optim.SGD momentum/wd step (dassl optim/optimizer.py:105-113)
  *   clipk_sgd_step_multi  the same over a param group's tensors in one launch
@@ -462,6 +464,39 @@ int clipk_src_head(int B, int C, int E, const float* img, const float* txt, cons
                    const float* alpha, float gamma, int focal, float scale, float w_text,
                    float w_image, float w_logits, float grad_scale, float* loss, float* logits,
                    float* d_img, float* d_txt, void* ws, void* stream);
+
+/* Linear-probe head (csrc/probe.hip): nn.Linear on frozen image features, CE / focal, and the
+ * gradients of the classifier, all fp32 and contiguous: feat [B,E], w [C,E], bias [C] or NULL,
+ * alpha [C] or NULL.
+ *   u_b     = normalize ? feat_b / max(|feat_b|, 1e-12) (F.normalize) : feat_b,
+ *   s[b,c]  = scale <u_b, w_c> + (bias ? bias[c] : 0);  logits [B,C] (optional) receives s,
+ *   loss[0] = (1/B) sum_b L(s_b, labels_b), L the CE / focal row loss of clipk_ce_loss (alpha, gamma,
+ *             focal: the same arithmetic).
+ * With G = d loss / d s = wgt_b / B (softmax(s_b) - onehot(labels_b)) (wgt_b = 1 for CE, the focal
+ * weight of the row otherwise) and d_w given,
+ *   d_w [C,E]  = grad_scale * scale * sum_b G[b,c] u[b,e],   d_bias [C] = grad_scale * sum_b G[b,c];
+ * nothing goes to feat (the encoder is frozen). d_bias must be given exactly when d_w and bias both
+ * are. d_w NULL: forward only, no gradient work is launched. labels NULL: scoring only -- logits
+ * (then required) is written and nothing else; loss, d_w and d_bias must be NULL, ws is not used and
+ * may be NULL.
+ * fp32 products and sums throughout (fp32 VALU FMA chains, no MFMA: DESIGN.md, "Probe head kernel"),
+ * the log-sum-exp kept as (row max, log of the sum), every sum in an order fixed by (B, C, E)
+ * (bitwise reproducible, no atomics). 3 launches with gradients (logits; row softmax, loss and G;
+ * d_w / d_bias and the loss sum), 2 forward only, 1 scoring only. C = 1 gives loss == 0, d_w == 0
+ * and d_bias == 0 exactly. A label outside [0, C) is never dereferenced: the loss (and that row's
+ * gradient) is NaN. 16-byte loads when E % 4 == 0 and feat / w are 16-byte aligned, one float at a
+ * time otherwise.
+ * ws: caller workspace of clipk_probe_head_ws_bytes(B, C, E) bytes (0 for a shape out of range),
+ * 16-byte aligned; no allocation or synchronisation inside. Any C >= 1 and E >= 1, 1 <= B <= 512
+ * (else CLIPK_ESHAPE). CLIPK_EINVAL: feat or w null; with labels: loss or ws null, the d_w / d_bias /
+ * bias rule broken, focal with gamma < 0; without labels: logits null or one of loss, d_w, d_bias
+ * given; scale <= 0. Checked on the host before any launch. */
+size_t clipk_probe_head_ws_bytes(int B, int C, int E);
+int clipk_probe_head(int B, int C, int E, const float* feat, const float* w, const float* bias,
+                     const int64_t* labels, const float* alpha, float gamma, int focal,
+                     int normalize, float scale, float grad_scale,
+                     float* loss, float* logits, float* d_w, float* d_bias,
+                     void* ws, void* stream);
 
 /* CoCoOp Meta-Net: h = relu(x W1^T + b1); y = h W2^T + b2. x [B,V], W1 [Hd,V], W2 [Wd,Hd].
  * The CLIP widths (V % 256 == 0, V <= 1024, Hd <= 64, x / W1 16-B aligned) take the
