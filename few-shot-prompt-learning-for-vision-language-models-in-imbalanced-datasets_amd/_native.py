@@ -51,6 +51,7 @@ _L = ctypes.c_long
 _F = ctypes.c_float
 _S = ctypes.c_size_t
 _D = ctypes.c_double
+_U = ctypes.c_uint
 
 # name -> (restype, argtypes); must match include/clipk.h exactly
 SIGNATURES = {
@@ -128,6 +129,10 @@ SIGNATURES = {
     "clipk_encoder_set_split": (_I, [_P, _I]),
     "clipk_encoder_set_split_target": (_I, [_P, _I]),
     "clipk_encoder_set_status": (_I, [_P, _P]),
+    "clipk_lora_merge": (_I, [_I, _I, _I, _I, _U, _F, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "clipk_lora_wgrad_ws_bytes": (_S, [_I, _I, _I]),
+    "clipk_lora_wgrad": (_I, [_I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _S, _P]),
+    "clipk_encoder_set_lora": (_I, [_P, _I, _I, _U, _F, _P, _P, _P, _P]),
     "clipk_vit_prompted_saved_bytes": (_S, [_P, _I, _I]),
     "clipk_vit_prompted_ws_bytes": (_S, [_P, _I, _I]),
     "clipk_vit_forward_prompted": (_I, [_P, _I, _P, _I, _P, _P, _P, _S, _P, _S, _P]),

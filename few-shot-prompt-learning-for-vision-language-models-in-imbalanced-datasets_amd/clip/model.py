@@ -270,6 +270,78 @@ def check_split_status(device=None):
             st.check()
 
 
+class LoraSpec:
+    """LoRA on attn.in_proj_weight of one encoder (clipk_lora_*, include/clipk.h): rank, scale =
+    ALPHA / RANK, proj_mask (bit 0 q, 1 k, 2 v) and layer_mask (bit l = layer l)."""
+
+    def __init__(self, rank, scale, proj_mask, layer_mask):
+        if not 1 <= int(rank) <= ops.LORA_MAX_RANK:
+            raise ValueError(f"LoRA rank must be in 1..{ops.LORA_MAX_RANK}, got {rank}")
+        if not 1 <= int(proj_mask) <= 7 or int(layer_mask) <= 0:
+            raise ValueError("LoRA needs at least one projection and one layer")
+        self.rank, self.scale = int(rank), float(scale)
+        self.proj_mask, self.layer_mask = int(proj_mask), int(layer_mask)
+
+
+def lora_init(layers, rank, width, generator=None, device="cpu"):
+    """Fresh adapters (A [layers, 3, r, W], B [layers, 3, W, r]) in fp32: A kaiming_uniform(a=sqrt 5),
+    i.e. U(-1 / sqrt W, 1 / sqrt W) (fan_in = W), B zero -- loralib's init."""
+    bound = 1.0 / float(width) ** 0.5
+    A = (torch.rand(layers, 3, rank, width, generator=generator) * 2 - 1) * bound
+    return A.to(device), torch.zeros(layers, 3, width, rank, device=device)
+
+
+class _LoraTables:
+    """The merged in_proj tables of a LoRA encoder: the fp32 base weights W0, the table tensors the
+    handle points at (entries 2 and 12: W' in the act dtype, W'^T in the grad dtype; PREC fp32s:
+    their split packings, filled from fp32 staging by ops.split_pack) and merge(), which rewrites
+    them in place."""
+
+    def __init__(self, spec, w0, act, grad, split, with_grad, device):
+        self.spec, self.w0, self.split = spec, w0, split
+        nl, W = len(w0), w0[0].shape[1]
+        self.layers, self.W = nl, W
+        mk = lambda shape, dt: [torch.empty(shape, dtype=dt, device=device) for _ in range(nl)]
+        if split:
+            self.stage = mk((3 * W, W), torch.float32)
+            self.stageT = mk((W, 3 * W), torch.float32) if with_grad else None
+            self.out = mk((3 * W, W), torch.int32)
+            self.outT = mk((W, 3 * W), torch.int32) if with_grad else None
+        else:
+            self.out = mk((3 * W, W), act)
+            self.outT = mk((W, 3 * W), grad) if with_grad else None
+        self.merges = 0
+        # until the first merge(A, B): B = 0, the tables hold W0
+        self.A0 = torch.zeros(nl, 3, spec.rank, W, device=device)
+        self.B0 = torch.zeros(nl, 3, W, spec.rank, device=device)
+        self.merge(self.A0, self.B0)
+
+    def merge(self, A, B):
+        """Tables <- W0 + scale B A (one clipk_lora_merge launch; PREC fp32s: + one split_pack per
+        table)."""
+        sp = self.spec
+        if self.split:
+            ops.lora_merge(self.w0, A, B, sp.proj_mask, sp.layer_mask, sp.scale, self.stage, self.stageT)
+            for src, dst in zip(self.stage + (self.stageT or []), self.out + (self.outT or [])):
+                ops.split_pack(src, out=dst)  # mode 1: merged weights are not fp16-valued
+        else:
+            ops.lora_merge(self.w0, A, B, sp.proj_mask, sp.layer_mask, sp.scale, self.out, self.outT)
+        self.merges += 1
+
+    def attach(self, handle, A=None, B=None, dA=None, dB=None):
+        """clipk_encoder_set_lora with these adapters (and gradient buffers) for the next calls."""
+        sp = self.spec
+        self._attached = (A, B, dA, dB)  # the handle keeps the pointers
+        ops.encoder_set_lora(handle, sp.rank, sp.proj_mask, sp.layer_mask, sp.scale,
+                             self.A0 if A is None else A, self.B0 if B is None else B, dA, dB)
+
+    def grads(self, handle, A, B):
+        """Fresh (dA, dB) buffers attached to the handle for a backward."""
+        dA, dB = torch.empty_like(A), torch.empty_like(B)
+        self.attach(handle, A, B, dA, dB)
+        return dA, dB
+
+
 class _Encoder:
     handle = None
 
@@ -285,7 +357,10 @@ class _Encoder:
 class TextEncoderCore(_Encoder):
     """Packed text transformer + ln_final + projection; native fwd / input-grad bwd."""
 
-    def __init__(self, sd, arch: ClipArch, prec: str, device, with_grad: bool = True):
+    def __init__(self, sd, arch: ClipArch, prec: str, device, with_grad: bool = True, lora: LoraSpec = None,
+                 ln_fold: bool = True):
+        """``lora``: the in_proj tables are merged LoRA weights (_LoraTables, ``self.lora``), built
+        without the LayerNorm fold; ``ln_fold`` False: no fold either way (the plain path)."""
         act, grad = prec_dtypes(prec)
         self.arch, self.prec, self.device = arch, prec, torch.device(device)
         self.act, self.grad = act, grad
@@ -296,7 +371,12 @@ class TextEncoderCore(_Encoder):
         table = []
         # LayerNorm fold of ln_1 / ln_2 into in_proj / c_fc (16-bit encoders and PREC fp32s;
         # clipk_encoder_set_ln_fold)
-        fold = [] if (act != torch.float32 or split) and ln_fold_enabled() else None
+        fold = [] if (act != torch.float32 or split) and ln_fold_enabled() and ln_fold and lora is None else None
+        self.lora = None
+        if lora is not None:
+            w0 = [_t(sd[f"transformer.resblocks.{i}.attn.in_proj_weight"]).float().to(self.device).contiguous()
+                  for i in range(nl)]
+            self.lora = _LoraTables(lora, w0, act, grad, split, with_grad, self.device)
         params = []
         for i in range(nl):
             p = {k: _t(sd[f"transformer.resblocks.{i}.{k}"]).float() for k in _LAYER_KEYS}
@@ -310,6 +390,9 @@ class TextEncoderCore(_Encoder):
                    A(p["mlp.c_proj.weight"]), f32(p["mlp.c_proj.bias"]),
                    G(p["attn.in_proj_weight"]), G(p["attn.out_proj.weight"]), G(p["mlp.c_fc.weight"]),
                    G(p["mlp.c_proj.weight"])]
+            if self.lora is not None:
+                row[2] = self.lora.out[i]
+                row[12] = self.lora.outT[i] if with_grad else None
             keep += row
             table += row
         P = _t(sd["text_projection"]).float()
@@ -321,7 +404,7 @@ class TextEncoderCore(_Encoder):
         self._keep = keep
         # PREC fp32s split mode (2: fp16-valued weights, CLIPK_F32S16), decided before the fold:
         # mode 2 folds gamma into A (clipk_gemm_ln_gamma) so B stays the fp16-valued W
-        self.split_mode = split_mode(keep) if split else 0
+        self.split_mode = (1 if self.lora is not None else split_mode(keep)) if split else 0
         if self.split_mode == 2:  # the tables hold the compact weights (clipk_encoder_set_split)
             table, head = compact16(table), compact16(head)
             keep = table + head
@@ -351,6 +434,8 @@ class TextEncoderCore(_Encoder):
         if fold:
             self._keep += fold
             N.check(N.load().clipk_encoder_set_ln_fold(h, _ptrs(fold)), "clipk_encoder_set_ln_fold")
+        if self.lora is not None:
+            self.lora.attach(h)
 
     def set_deep(self, deep, rows, n_per, grads=None):
         """Deep prompts for the next call(s): deep fp32 [n_deep, n_ctx, W] (None clears)."""
@@ -466,6 +551,39 @@ class TextEncodeFn(torch.autograd.Function):
         return dx0, None, None
 
 
+class LoraTextEncodeFn(torch.autograd.Function):
+    """(A, B, x0) -> text features through a LoRA text encoder whose tables were merged from these
+    A [layers, 3, r, W], B [layers, 3, W, r] (core.lora.merge; the caller merges once per parameter
+    version). The backward returns dA, dB (clipk_lora_wgrad inside clipk_text_backward); the input
+    gradient dx0 is discarded: the token embeddings are frozen."""
+
+    @staticmethod
+    def forward(ctx, A, B, x0, core, shape):
+        if shape.packed:
+            raise RuntimeError("LoRA runs on the plain text layout only")
+        A, B = A.contiguous(), B.contiguous()
+        need = any(ctx.needs_input_grad[:2])
+        core.lora.attach(core.handle, A, B)
+        txt, saved = core.forward(x0.contiguous(), shape, save=need)
+        ctx.core, ctx.shape, ctx.saved_arena = core, shape, saved
+        ctx.save_for_backward(A, B)
+        return txt
+
+    @staticmethod
+    def backward(ctx, dtxt):
+        if ctx.saved_arena is None:
+            raise RuntimeError("text encoder backward without saved activations")
+        A, B = ctx.saved_tensors
+        core = ctx.core
+        dA, dB = core.lora.grads(core.handle, A, B)
+        try:
+            core.backward(dtxt, ctx.shape, ctx.saved_arena)
+        finally:
+            core.lora.attach(core.handle, A, B)
+        ctx.saved_arena = None
+        return dA, dB, None, None, None
+
+
 def deep_text_rows(shape, n_ctx, device):
     """Rows the text deep prompts replace (tokens 1..n_ctx of every sequence, model.py:244-252),
     as the [n_ctx][n_per] table of clipk_rows_inject: packed layout -> prefix rows of each group."""
@@ -514,7 +632,9 @@ class VisionEncoder(nn.Module, _Encoder):
     weights; ``with_grad`` packs the transposed layer weights for the prompted input-grad
     backward (forward_prompted / PromptedVisionFn)."""
 
-    def __init__(self, sd, arch: ClipArch, prec: str, device, with_grad: bool = False):
+    def __init__(self, sd, arch: ClipArch, prec: str, device, with_grad: bool = False, lora: LoraSpec = None,
+                 ln_fold: bool = True):
+        """``lora`` / ``ln_fold``: as TextEncoderCore's."""
         nn.Module.__init__(self)
         act, _ = PREC_DTYPES[prec]
         split = prec == "fp32s"
@@ -529,7 +649,11 @@ class VisionEncoder(nn.Module, _Encoder):
         table = []
         # LayerNorm fold of ln_1 / ln_2 for the layer-loop forward (clipk_vit_forward: 16-bit
         # residual stream, or PREC fp32s's fp32 one), built once the split mode is known
-        fparams = [] if (act != torch.float32 or split) and ln_fold_enabled() else None
+        fparams = [] if (act != torch.float32 or split) and ln_fold_enabled() and ln_fold and lora is None else None
+        object.__setattr__(self, "lora", None)
+        if lora is not None:
+            w0 = [f32(sd[f"visual.transformer.resblocks.{i}.attn.in_proj_weight"]) for i in range(nl)]
+            object.__setattr__(self, "lora", _LoraTables(lora, w0, act, act, split, with_grad, self.dev))
         for i in range(nl):
             pre = f"visual.transformer.resblocks.{i}."
             q = {k: sd[pre + k] for k in _LAYER_KEYS}
@@ -541,6 +665,9 @@ class VisionEncoder(nn.Module, _Encoder):
                       A(q["mlp.c_proj.weight"]), f32(q["mlp.c_proj.bias"]),
                       G(q["attn.in_proj_weight"]), G(q["attn.out_proj.weight"]), G(q["mlp.c_fc.weight"]),
                       G(q["mlp.c_proj.weight"])]
+            if self.lora is not None:
+                table[-14] = self.lora.out[i]
+                table[-4] = self.lora.outT[i] if with_grad else None
         k = 3 * p * p
         kq = 32 if act == torch.float32 else 64
         self.Kp = (k + kq - 1) // kq * kq
@@ -553,7 +680,8 @@ class VisionEncoder(nn.Module, _Encoder):
                 f32(sd["visual.positional_embedding"])]
         # backward of the head: d ln_post(CLS) = dfeat . proj^T  (proj [D, E], B operand [N=D, K=E])
         self.proj_bwd = _mm_weight(_t(sd["visual.proj"]).float(), self.dev, act, split) if with_grad else None
-        self.split_mode = split_mode([t for t in table if t is not None] + head + [self.proj_bwd]) if split else 0
+        self.split_mode = (1 if self.lora is not None else
+                           split_mode([t for t in table if t is not None] + head + [self.proj_bwd])) if split else 0
         if self.split_mode == 2:  # the tables hold the compact weights (clipk_encoder_set_split)
             table, head = compact16(table), compact16(head)
             self.proj_bwd = compact16([self.proj_bwd])[0]
@@ -587,6 +715,8 @@ class VisionEncoder(nn.Module, _Encoder):
         if fold:
             self._keep += fold
             N.check(N.load().clipk_encoder_set_ln_fold(h, _ptrs(fold)), "clipk_encoder_set_ln_fold")
+        if self.lora is not None:
+            self.lora.attach(h)
 
     def _check_image(self, image):
         image = image.to(self.dev, torch.float32).contiguous()
@@ -694,18 +824,54 @@ class PromptedVisionFn(torch.autograd.Function):
         return dvpt, ddeep, None, None
 
 
+class LoraVisionFn(torch.autograd.Function):
+    """(A, B, image) -> image features through a LoRA ViT (the prompted ViT's calls with no prompt
+    rows) whose tables were merged from these A, B; the backward returns dA, dB."""
+
+    @staticmethod
+    def forward(ctx, A, B, image, enc):
+        A, B = A.contiguous(), B.contiguous()
+        need = any(ctx.needs_input_grad[:2])
+        enc.lora.attach(enc.handle, A, B)
+        vpt = torch.zeros(0, enc.width, device=enc.dev)
+        feat, saved = enc.forward_prompted(image, vpt, None, save=need)
+        ctx.enc, ctx.saved_arena, ctx.B, ctx.vpt = enc, saved, image.shape[0], vpt
+        ctx.save_for_backward(A, B)
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        if ctx.saved_arena is None:
+            raise RuntimeError("image encoder backward without saved activations")
+        A, B = ctx.saved_tensors
+        enc = ctx.enc
+        dA, dB = enc.lora.grads(enc.handle, A, B)
+        try:
+            enc.backward_prompted(dfeat, ctx.vpt, None, ctx.saved_arena, ctx.B)
+        finally:
+            enc.lora.attach(enc.handle, A, B)
+        ctx.saved_arena = None
+        # PREC fp32s: read the overflow flag here, so that it is neither missed (ENCODER vision) nor
+        # taken by the text backward for its own
+        if enc._status is not None and enc._status.read():
+            raise N.ClipkError("PREC fp32s LoRA image encoder backward: non-finite adapter gradients (gradient "
+                               "growth beyond fp16's range in the split-fp16 GEMM operands); use PREC fp32")
+        return dA, dB, None, None
+
+
 class CLIP(nn.Module):
     """Container with the attributes the prompt learners read (model.py:488-561)."""
 
-    def __init__(self, sd, prec: str = "fp16", device="cuda", text_grad: bool = True, vision_grad: bool = False):
+    def __init__(self, sd, prec: str = "fp16", device="cuda", text_grad: bool = True, vision_grad: bool = False,
+                 text_lora: LoraSpec = None, vision_lora: LoraSpec = None, ln_fold: bool = True):
         super().__init__()
         if prec not in PREC_DTYPES:
             raise AssertionError(f"PREC must be one of {list(PREC_DTYPES)}")
         arch = arch_from_state_dict(sd)
         self.arch, self.prec = arch, prec
         dev = torch.device(device)
-        self.visual = VisionEncoder(sd, arch, prec, dev, with_grad=vision_grad)
-        self.text = TextEncoderCore(sd, arch, prec, dev, with_grad=text_grad)
+        self.visual = VisionEncoder(sd, arch, prec, dev, with_grad=vision_grad, lora=vision_lora, ln_fold=ln_fold)
+        self.text = TextEncoderCore(sd, arch, prec, dev, with_grad=text_grad, lora=text_lora, ln_fold=ln_fold)
         W = arch.transformer_width
         self.token_embedding = nn.Embedding(arch.vocab_size, W)
         with torch.no_grad():
@@ -724,7 +890,10 @@ class CLIP(nn.Module):
 
 
 def build_model(state_dict, prec: str = "fp16", device="cuda", text_grad: bool = True,
-                vision_grad: bool = False) -> CLIP:
+                vision_grad: bool = False, text_lora: LoraSpec = None, vision_lora: LoraSpec = None,
+                ln_fold: bool = True) -> CLIP:
     """build_model(state_dict) analogue (model.py:662-705) for the native path; vision_grad
-    packs the ViT's backward weights (trainers whose visual prompts train)."""
-    return CLIP(state_dict, prec=prec, device=device, text_grad=text_grad, vision_grad=vision_grad)
+    packs the ViT's backward weights (trainers whose visual prompts or adapters train); text_lora /
+    vision_lora: LoRA encoders (LoraSpec); ln_fold False: encoders without the LayerNorm fold."""
+    return CLIP(state_dict, prec=prec, device=device, text_grad=text_grad, vision_grad=vision_grad,
+                text_lora=text_lora, vision_lora=vision_lora, ln_fold=ln_fold)

@@ -47,6 +47,16 @@ struct clipk_encoder {
   int split = 0;
   int split_target = 7;     // the backward's gradient scale puts max |s dtxt| in [2^(t-1), 2^t)
   int* status = nullptr;    // clipk_encoder_set_status: overflow flags of split calls (device)
+  // clipk_encoder_set_lora: the tables' in_proj weights (2, 12) are merged LoRA weights
+  // (clipk_lora_merge); the backward also forms the adapters' gradients (clipk_lora_wgrad) for the
+  // layers of layer_mask. A, dA [layers][3][rank][W], B, dB [layers][3][W][rank] fp32 (rank 0: off)
+  struct Lora {
+    int rank = 0, proj_mask = 0;
+    unsigned layer_mask = 0;
+    float scale = 0.f;
+    const float *A = nullptr, *B = nullptr;
+    float *dA = nullptr, *dB = nullptr;
+  } lora;
 };
 
 namespace clipk {
@@ -255,6 +265,8 @@ struct TextBwdBufs {
   float* dlnf;
   float* gscale;  // PREC fp32s: the backward's gradient scale s and 1 / s (+ amax partials)
   void* part;  // shared-prefix attention: per-chunk prefix dK/dV partials
+  void* lora;  // clipk_lora_wgrad's workspace (LoRA set on the encoder)
+  size_t lora_bytes;
   size_t bytes;
 };
 
@@ -272,6 +284,8 @@ static TextBwdBufs text_bwd_layout(const clipk_encoder* e, size_t rows, int nout
   b.dqkv = c.take(rows * 3 * W * g);
   b.part = part_bytes ? c.take(part_bytes) : nullptr;
   b.gscale = (float*)c.take((2 + kAmaxBlocks) * sizeof(float));
+  b.lora_bytes = e->lora.rank > 0 ? clipk_lora_wgrad_ws_bytes((int)rows, (int)W, e->lora.rank) : 0;
+  b.lora = b.lora_bytes ? c.take(b.lora_bytes) : nullptr;
   b.bytes = c.off;
   return b;
 }
@@ -973,6 +987,16 @@ static int text_backward_impl(const clipk_encoder* e, const SeqShape& sh, const 
   };
   // the forward saved quickgelu'(h) in t.h (CLIPK_QGELU_DERIV)
   const int dgelu_epi = CLIPK_EPI_DQGELU | CLIPK_QGELU_DERIV;
+  // LoRA: the adapters' gradients of this backward (per layer, [3][rank][W] floats each way)
+  const clipk_encoder::Lora& lo = e->lora;
+  const bool lora_grad = lo.rank > 0 && lo.dA && lo.dB;
+  const size_t lora_n = (size_t)3 * lo.rank * W;
+  if (lora_grad)
+    for (int l = 0; l < e->layers; ++l)
+      if (!((lo.layer_mask >> l) & 1u)) {  // the layers without adapters: zeros
+        TRY(zero(lo.dA + l * lora_n, lora_n * 4));
+        TRY(zero(lo.dB + l * lora_n, lora_n * 4));
+      }
   for (int l = e->layers - 1; l >= 0; --l) {
     const auto& w = e->lw[l];
     if (!w[12] || !w[13] || !w[14] || !w[15]) return CLIPK_EINVAL;
@@ -1016,6 +1040,13 @@ static int text_backward_impl(const clipk_encoder* e, const SeqShape& sh, const 
       TRY(attn_bwd(e, sh, t.qkv[l], t.o[l], b.do_, t.lse[l], b.dqkv, b.part, st, qkv_split,
                    shared0 ? CLIPK_PREFIX_CLS_GROUP0 : 0));
     }
+    if (lora_grad && ((lo.layer_mask >> l) & 1u)) {
+      // algorithmic: X and dq|dk|dv read twice (the rows pass and the partial sums)
+      ProfScope ps(CLIPK_PROF_NONE, st, 0.0, SITE("lora_wgrad"), 2.0 * rows * W * (esize(rd) + 3.0 * esize(gd)));
+      TRY(clipk_lora_wgrad(rd, gd, rows, W, lo.rank, lo.proj_mask, lo.scale, t.X[l], t.mean1[l], t.rstd1[l],
+                           (const float*)w[0], (const float*)w[1], b.dqkv, lo.A + l * lora_n, lo.B + l * lora_n,
+                           lo.dA + l * lora_n, lo.dB + l * lora_n, b.lora, b.lora_bytes, st));
+    }
     if (l == 0 && io.text && prefix_mode(e, sh)) {
       // the input gradient on the prefix rows only: dqkv gathered to G*P compact rows, their
       // qkv input-grad GEMM and LN1 backward (scattered back to the prefix rows of dx0)
@@ -1055,6 +1086,10 @@ static int text_backward_impl(const clipk_encoder* e, const SeqShape& sh, const 
     TRY(grad_scale_out((long)rows * W, dX, b.gscale, st));
     const DeepPrompts& d = e->deep;
     if (d.n_deep > 0 && d.grads) TRY(grad_scale_out((long)d.n_deep * d.n_ctx * W, d.grads, b.gscale, st));
+    if (lora_grad) {
+      TRY(grad_scale_out((long)(e->layers * lora_n), lo.dA, b.gscale, st));
+      TRY(grad_scale_out((long)(e->layers * lora_n), lo.dB, b.gscale, st));
+    }
     // the returned gradients must be finite (prefix-input mode: only the prefix rows of dx0 are
     // specified)
     if (io.text && prefix_mode(e, sh))
@@ -1062,6 +1097,10 @@ static int text_backward_impl(const clipk_encoder* e, const SeqShape& sh, const 
     else
       TRY(split_check(e, 1, (long)rows * W, 0, dX, 2, st));
     if (d.n_deep > 0 && d.grads) TRY(split_check(e, 1, (long)d.n_deep * d.n_ctx * W, 0, d.grads, 2, st));
+    if (lora_grad) {
+      TRY(split_check(e, 1, (long)(e->layers * lora_n), 0, lo.dA, 2, st));
+      TRY(split_check(e, 1, (long)(e->layers * lora_n), 0, lo.dB, 2, st));
+    }
   }
   return CLIPK_OK;
 }
@@ -1134,6 +1173,7 @@ extern "C" int clipk_text_forward_packed(const clipk_encoder* e, int G, int C, i
                                          void* ws, size_t ws_bytes, void* stream) {
   if (!e || e->kind != 0 || !tiles || !row_first || !x0 || !eot_rows || !txt || !ws) return CLIPK_EINVAL;
   if (!packed_ok(G, C, P, R, ntiles)) return CLIPK_ESHAPE;
+  if (e->lora.rank > 0) return CLIPK_EINVAL;  // LoRA: the plain layouts only
   return text_forward_impl(e, SeqShape::prefix(G, C, P, R, ntiles, tiles, row_first), x0, eot_rows, txt, saved,
                            saved_bytes, ws, ws_bytes, (hipStream_t)stream, text_io(e));
 }
@@ -1146,6 +1186,7 @@ extern "C" int clipk_text_backward_packed(const clipk_encoder* e, int G, int C, 
     return CLIPK_EINVAL;
   if (!e->head[3]) return CLIPK_EINVAL;
   if (!packed_ok(G, C, P, R, ntiles)) return CLIPK_ESHAPE;
+  if (e->lora.rank > 0) return CLIPK_EINVAL;
   return text_backward_impl(e, SeqShape::prefix(G, C, P, R, ntiles, tiles, row_first), eot_rows, dtxt, saved,
                             saved_bytes, dx0, ws, ws_bytes, (hipStream_t)stream, text_io(e));
 }
@@ -1368,6 +1409,7 @@ extern "C" int clipk_encoder_set_ln_fold(clipk_encoder* e, const void* const* fo
     e->fold.clear();
     return CLIPK_OK;
   }
+  if (e->lora.rank > 0) return CLIPK_EINVAL;  // the fold tables hold W0, not the merged weights
   if (e->act == CLIPK_F32 && !e->split) return CLIPK_EDTYPE;  // fp32s: call after set_split
   std::vector<std::array<const void*, 6>> f(e->layers);
   for (int l = 0; l < e->layers; ++l)
@@ -1402,11 +1444,28 @@ extern "C" int clipk_encoder_set_status(clipk_encoder* e, int* status) {
   return CLIPK_OK;
 }
 
+extern "C" int clipk_encoder_set_lora(clipk_encoder* e, int rank, int proj_mask, unsigned layer_mask, float scale,
+                                      const float* A, const float* B, float* dA, float* dB) {
+  if (!e || rank < 0) return CLIPK_EINVAL;
+  if (rank == 0) {
+    e->lora = clipk_encoder::Lora();
+    return CLIPK_OK;
+  }
+  if (rank > 16 || proj_mask < 1 || proj_mask > 7 || !A || !B || (dA == nullptr) != (dB == nullptr)) return CLIPK_EINVAL;
+  if (e->layers > 32 || (e->layers < 32 && (layer_mask >> e->layers))) return CLIPK_EINVAL;
+  if (!e->fold.empty() || e->deep.n_deep > 0) return CLIPK_EINVAL;
+  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)dA | (uintptr_t)dB) & 15) return CLIPK_EINVAL;
+  e->lora.rank = rank; e->lora.proj_mask = proj_mask; e->lora.layer_mask = layer_mask; e->lora.scale = scale;
+  e->lora.A = A; e->lora.B = B; e->lora.dA = dA; e->lora.dB = dB;
+  return CLIPK_OK;
+}
+
 extern "C" int clipk_encoder_set_deep_prompts(clipk_encoder* e, int n_deep, int n_ctx, int n_per, const int* rows,
                                               const float* prompts, float* grads) {
   if (!e) return CLIPK_EINVAL;
   if (n_deep < 0 || n_deep >= e->layers || (n_deep > 0 && (n_ctx <= 0 || n_per <= 0))) return CLIPK_ESHAPE;
   if (n_deep > 0 && (!rows || !prompts)) return CLIPK_EINVAL;
+  if (n_deep > 0 && e->lora.rank > 0) return CLIPK_EINVAL;
   e->deep = DeepPrompts();
   if (n_deep > 0) {
     e->deep.n_deep = n_deep; e->deep.n_ctx = n_ctx; e->deep.n_per = n_per;
@@ -1430,6 +1489,7 @@ extern "C" int clipk_vit_forward_prompted(const clipk_encoder* e, int B, const f
                                           size_t ws_bytes, void* stream) {
   if (!e || e->kind != 1 || !img || !feat || !ws || (n_vpt > 0 && !vpt)) return CLIPK_EINVAL;
   if (B <= 0 || n_vpt < 0) return CLIPK_ESHAPE;
+  if (e->lora.rank > 0 && n_vpt > 0) return CLIPK_EINVAL;  // LoRA: the plain layouts only
   SplitScope split_scope(e);
   VitPBufs v = vitp_layout(e, B, n_vpt, ws);
   if (ws_bytes < v.bytes) return CLIPK_EWORKSPACE;
@@ -1457,6 +1517,7 @@ extern "C" int clipk_vit_backward_prompted(const clipk_encoder* e, int B, int n_
   if (!e || e->kind != 1 || !proj_bwd || !dfeat || !saved || !ws || (n_vpt > 0 && (!vpt || !dvpt)))
     return CLIPK_EINVAL;
   if (B <= 0 || n_vpt < 0) return CLIPK_ESHAPE;
+  if (e->lora.rank > 0 && n_vpt > 0) return CLIPK_EINVAL;
   for (int l = 0; l < e->layers; ++l)
     if (!e->lw[l][12] || !e->lw[l][13] || !e->lw[l][14] || !e->lw[l][15]) return CLIPK_EINVAL;
   VitPBufs v = vitp_layout(e, B, n_vpt, ws);

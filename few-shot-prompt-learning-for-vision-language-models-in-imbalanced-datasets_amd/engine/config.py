@@ -148,6 +148,13 @@ def get_cfg_default() -> CfgNode:
             "LINEAR_PROBE": {"PREC": "fp16", "LOSS_TYPE": "ce", "NORMALIZE": True, "BIAS": True,
                              "INIT": "zeroshot", "LOGIT_SCALE": 0.0, "CACHE_FEATURES": False,
                              "CACHE_SHUFFLE": True},
+            # this package's LoRA (trainers/lora.py; CLIP-LoRA's q / k / v adapters): W' = W0 +
+            # ALPHA / RANK * B A on attn.in_proj_weight. PARAMS: a subset of q, k, v (o and the MLP:
+            # unsupported); ENCODER both / text / vision; POSITION all / bottom / mid / up /
+            # half-bottom / half-up / top3 (CLIP-LoRA's layer sets); DROPOUT_RATE must be 0 (dropout
+            # on the adapter input cannot be expressed with merged weights)
+            "LORA": {"RANK": 2, "ALPHA": 1, "PARAMS": ["q", "k", "v"], "ENCODER": "both", "POSITION": "all",
+                     "DROPOUT_RATE": 0.0, "PREC": "fp16", "LOSS_TYPE": "ce"},
         },
         # MI355X-native knobs (not in the reference): prompt truncation to the EOT and the
         # max rows per text-encoder launch chunk (memory bound for large B*C).

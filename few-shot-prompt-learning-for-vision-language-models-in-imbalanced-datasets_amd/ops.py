@@ -35,14 +35,18 @@ def _need(t, name, dtype=None, cuda=True):
     return t
 
 
-def split_pack(w):
+def split_pack(w, out=None):
     """clipk_split_pack: fp32 weight [N, K] -> its split-fp16 packing for PREC fp32s
-    (SPLIT_SCALE * w as fp16 hi + lo parts, 4 bytes per element; int32 storage [N, K])."""
+    (SPLIT_SCALE * w as fp16 hi + lo parts, 4 bytes per element; int32 storage [N, K]; ``out``:
+    an existing packing to overwrite)."""
     _need(w, "W", torch.float32)
     n, k = w.shape
     if k % 32:
         raise N.ClipkError(f"split_pack needs K % 32 == 0, got {k}")
-    out = torch.empty(n, k, dtype=torch.int32, device=w.device)
+    if out is None:
+        out = torch.empty(n, k, dtype=torch.int32, device=w.device)
+    elif _need(out, "out", torch.int32).shape != w.shape:
+        raise N.ClipkError("split_pack: out must have W's shape")
     # the library checks |W| < 65504 / SPLIT_SCALE itself (CLIPK_ERANGE)
     N.call("clipk_split_pack", n, k, _p(w), k, _p(out), _stream())
     return out
@@ -734,3 +738,69 @@ def rows_collect(src, rows, n_ctx, n_per, out=None, zero_src=True, src2=None):
            DT[src2.dtype] if src2 is not None else 0, W if src2 is not None else 0, _p(rows), _p(out), int(acc),
            int(zero_src), _stream())
     return out
+
+
+LORA_PROJ_BITS = {"q": 1, "k": 2, "v": 4}  # proj_mask bits of clipk_lora_*
+LORA_MAX_RANK = 16
+
+
+def lora_merge(w0, A, B, proj_mask, layer_mask, scale, out, outT=None):
+    """clipk_lora_merge: out[l] = W0[l] + scale * B[l] A[l] on the masked projections / layers
+    (else W0[l]) and outT[l] its transpose, in one launch. w0: list of fp32 [3W, W]; A fp32
+    [layers, 3, r, W]; B fp32 [layers, 3, W, r]; out / outT: lists of [3W, W] / [W, 3W] tensors
+    (one dtype each: fp32, fp16 or bf16), written in place."""
+    layers = len(w0)
+    _need(A, "A", torch.float32)
+    _need(B, "B", torch.float32)
+    r, W = A.shape[-2], A.shape[-1]
+    if tuple(A.shape) != (layers, 3, r, W) or tuple(B.shape) != (layers, 3, W, r):
+        raise N.ClipkError(f"lora_merge: A {tuple(A.shape)} / B {tuple(B.shape)} do not match {layers} layers")
+    if len(out) != layers or (outT is not None and len(outT) != layers):
+        raise N.ClipkError("lora_merge: one output per layer")
+    for t in w0:
+        _need(t, "W0", torch.float32)
+        if tuple(t.shape) != (3 * W, W):
+            raise N.ClipkError(f"lora_merge: W0 must be [{3 * W}, {W}], got {tuple(t.shape)}")
+    for t in out:
+        _need(t, "out", out[0].dtype)
+        if tuple(t.shape) != (3 * W, W):
+            raise N.ClipkError(f"lora_merge: out must be [{3 * W}, {W}], got {tuple(t.shape)}")
+    for t in outT or []:
+        _need(t, "outT", outT[0].dtype)
+        if tuple(t.shape) != (W, 3 * W):
+            raise N.ClipkError(f"lora_merge: outT must be [{W}, {3 * W}], got {tuple(t.shape)}")
+    VP = ctypes.c_void_p * layers
+    N.call("clipk_lora_merge", W, layers, r, int(proj_mask), int(layer_mask), float(scale), DT[out[0].dtype],
+           DT[outT[0].dtype] if outT else N.F32, VP(*[t.data_ptr() for t in w0]), _p(A), _p(B),
+           VP(*[t.data_ptr() for t in out]), VP(*[t.data_ptr() for t in outT]) if outT else None, _stream())
+    return out, outT
+
+
+def lora_wgrad(x, mean, rstd, gamma, beta, dqkv, A, B, proj_mask, scale, dA=None, dB=None):
+    """clipk_lora_wgrad: one layer's adapter gradients (dA [3, r, W], dB [3, W, r], fp32) from the
+    layer input x [rows, W], its LayerNorm statistics and weights, and dqkv [rows, 3W]."""
+    _need(x, "x")
+    _need(dqkv, "dqkv")
+    for t, nm in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (beta, "beta"), (A, "A"), (B, "B")):
+        _need(t, nm, torch.float32)
+    rows, W = x.shape
+    r = A.shape[-2]
+    if tuple(A.shape) != (3, r, W) or tuple(B.shape) != (3, W, r) or tuple(dqkv.shape) != (rows, 3 * W):
+        raise N.ClipkError(f"lora_wgrad: shapes x {tuple(x.shape)}, dqkv {tuple(dqkv.shape)}, A {tuple(A.shape)}, "
+                           f"B {tuple(B.shape)} do not match")
+    if mean.numel() != rows or rstd.numel() != rows or gamma.numel() != W or beta.numel() != W:
+        raise N.ClipkError("lora_wgrad: LayerNorm statistics / weights do not match x")
+    dA = torch.empty_like(A) if dA is None else _need(dA, "dA", torch.float32)
+    dB = torch.empty_like(B) if dB is None else _need(dB, "dB", torch.float32)
+    wsb = N.load().clipk_lora_wgrad_ws_bytes(rows, W, r)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=x.device)
+    N.call("clipk_lora_wgrad", DT[x.dtype], DT[dqkv.dtype], rows, W, r, int(proj_mask), float(scale), _p(x),
+           _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dqkv), _p(A), _p(B), _p(dA), _p(dB), _p(ws), ws.numel(),
+           _stream())
+    return dA, dB
+
+
+def encoder_set_lora(handle, rank, proj_mask=0, layer_mask=0, scale=0.0, A=None, B=None, dA=None, dB=None):
+    """clipk_encoder_set_lora on an encoder handle (rank 0 clears)."""
+    N.call("clipk_encoder_set_lora", handle, int(rank), int(proj_mask), int(layer_mask), float(scale), _p(A), _p(B),
+           _p(dA), _p(dB))

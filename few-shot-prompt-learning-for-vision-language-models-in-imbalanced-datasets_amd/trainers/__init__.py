@@ -1,3 +1,3 @@
-"""CoOp / CoCoOp / ZeroshotCLIP / IVLP / MaPLe / PromptSRC / LinearProbeCLIP trainers (registered in
+"""CoOp / CoCoOp / ZeroshotCLIP / IVLP / MaPLe / PromptSRC / LinearProbeCLIP / LoRA trainers (registered in
 fsp_amd.engine.TRAINER_REGISTRY)."""
-from . import coop, cocoop, zsclip, deep, linear_probe  # noqa: F401
+from . import coop, cocoop, zsclip, deep, linear_probe, lora  # noqa: F401

@@ -31,6 +31,9 @@
  *                         fwd+bwd (promptsrc.py:171-213, 296-323)
  *   clipk_probe_head      the linear probe's nn.Linear head on frozen image features plus
  *                         CE / focal, fwd+bwd (this package's LinearProbeCLIP)
+ *   clipk_lora_*          LoRA on attn.in_proj_weight: the merged weights W0 + s B A and the
+ *                         adapters' gradients (this package's LoRA; loralib's Linear / MergedLinear
+ *                         with merged weights, and autograd's dA / dB)
  *   clipk_meta_net_*      CoCoOp Meta-Net Linear-ReLU-Linear (cocoop.py:139-143,182-185)
  *   clipk_sgd_step        torch.optim.SGD momentum/wd step (dassl optim/optimizer.py:105-113)
  *   clipk_sgd_step_multi  the same over a param group's tensors in one launch
@@ -651,6 +654,45 @@ int clipk_encoder_set_split_target(clipk_encoder* e, int target);
  * it and reads it when it synchronises (fsp_amd/clip/model.py re-runs an overflowed backward at a
  * lower scale target). NULL detaches. The pointer must stay valid for the calls that follow. */
 int clipk_encoder_set_status(clipk_encoder* e, int* status);
+
+/* LoRA on attn.in_proj_weight (this package's LoRA trainer; CLIP-LoRA's q / k / v adapters):
+ *   W'_p = W0_p + scale * B_p A_p  for the projections p (bit 0 q, 1 k, 2 v) of proj_mask, in the
+ *   layers of layer_mask (bit l); A_p [rank, W], B_p [W, rank] fp32, 1 <= rank <= 16, W % 64 == 0.
+ * LoRA is linear, so an encoder whose tables hold W' (entries 2 and 12) runs LoRA's forward and its
+ * input-grad backward unchanged; what is new is the merge and the adapters' own gradient.
+ *
+ * clipk_lora_merge: one launch for all `layers` (<= 32) of an encoder. w0[l] fp32 [3W, W] (host
+ * array of device pointers, as out / outT); A [layers][3][rank][W], B [layers][3][W][rank].
+ * out[l] = W' [3W, W] in act_dtype, outT[l] = W'^T [W, 3W] in grad_dtype (outT NULL: none), both
+ * rounded once from the same fp32 value  fma(scale, acc, W0[n, k]),  acc = 0, then
+ * acc = fma(B[n, j], A[j, k], acc) for j ascending. Projections and layers outside the masks: W0.
+ * Output dtypes CLIPK_F32 / F16 / BF16 (PREC fp32s: merge to fp32, then clipk_split_pack).
+ *
+ * clipk_lora_wgrad: one layer's dA [3][rank][W], dB [3][W][rank] (fp32, overwritten; zeros for the
+ * projections outside proj_mask) from the layer input X [rows, W] (x_dtype), its LayerNorm
+ * statistics mean / rstd [rows], the LayerNorm's gamma / beta and dqkv [rows, 3W] (g_dtype):
+ *   xn = (X - mean) rstd gamma + beta    P_p = xn A_p^T    dU_p = scale dY_p B_p
+ *   dB_p = scale dY_p^T P_p              dA_p = dU_p^T xn            (dY_p: dqkv's p slice)
+ * fp32 accumulation in an order fixed by the shapes (bitwise reproducible), three launches.
+ * CLIPK_EINVAL: rank outside 1..16, W % 64 != 0, a null or misaligned (16 B) pointer.
+ *
+ * clipk_encoder_set_lora: declares the handle's in_proj tables merged as above; its backwards
+ * (clipk_text_backward, clipk_vit_backward_prompted with n_vpt = 0) then also write
+ * dA [layers][3][rank][W] and dB [layers][3][W][rank] (zeros for layers outside layer_mask; with
+ * PREC fp32s unscaled with dx0 and covered by status flag 2). dA = dB = NULL: no gradients.
+ * Query the backward workspace size after this call. The pointers must stay valid; rank = 0
+ * clears. CLIPK_EINVAL with a LayerNorm fold or deep prompts set (and from those setters while
+ * LoRA is set), and from the packed text entry points and prompted ViT calls with n_vpt > 0. */
+int clipk_lora_merge(int W, int layers, int rank, int proj_mask, unsigned layer_mask, float scale,
+                     int act_dtype, int grad_dtype, const float* const* w0, const float* A, const float* B,
+                     void* const* out, void* const* outT, void* stream);
+size_t clipk_lora_wgrad_ws_bytes(int rows, int W, int rank);
+int clipk_lora_wgrad(int x_dtype, int g_dtype, int rows, int W, int rank, int proj_mask, float scale,
+                     const void* X, const float* mean, const float* rstd, const float* gamma,
+                     const float* beta, const void* dqkv, const float* A, const float* B, float* dA,
+                     float* dB, void* ws, size_t ws_bytes, void* stream);
+int clipk_encoder_set_lora(clipk_encoder* e, int rank, int proj_mask, unsigned layer_mask, float scale,
+                           const float* A, const float* B, float* dA, float* dB);
 
 /* ViT with visual prompts, forward with saved activations and input-grad backward (the
  * prompted VisionTransformer of IVLP / PromptSRC, model.py:401-431, and MaPLe, 434-485):
