@@ -36,6 +36,7 @@ def source_digest():
 
 F32, F16, BF16, F32S = 0, 1, 2, 3  # F32S: fp32 activations x split-packed weights (PREC fp32s)
 PREFIX_CLS_GROUP0 = 1  # clipk_attention_prefix_*_ex flag
+PREFIX_SPLIT = 2  # ... fp32 tensors on the 16-bit MFMA as fp16 hi / lo parts (PREC fp32s)
 F32S16 = 4  # F32S for fp16-valued weights: B is the compact fp16 SPLIT_SCALE * W (clipk_split_hi16)
 SPLIT_SCALE = 64.0  # CLIPK_SPLIT_SCALE: clipk_split_pack stores SPLIT_SCALE * W
 EPI_BIAS, EPI_BIAS_RES, EPI_BIAS_QGELU, EPI_DQGELU, EPI_NONE = 0, 1, 2, 3, 4

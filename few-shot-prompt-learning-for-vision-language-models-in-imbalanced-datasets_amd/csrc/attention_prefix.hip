@@ -778,7 +778,8 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_bwd_lds(int G, int P, in
   }
 }
 
-// ------------------------------------------------------------------ fp32 kernels (PREC fp32 / fp32s)
+// ------------------------------------------------------------------ fp32 kernels (PREC fp32; fp32 calls
+// without CLIPK_PREFIX_SPLIT -- PREC fp32s runs attn_prefix_*_split below)
 // One wave per (group, chunk of f32_uc units, head); blocks of WPB waves (f32_wpb) share one
 // (group, head), so the prefix K/V rows are staged into LDS once per block. Lane = 4 r + s: row
 // r of the unit (query in the forward and for dQ, key for dK / dV) and 16-column slice s of
@@ -1092,6 +1093,384 @@ __global__ __launch_bounds__(WPB * 64, 2) void attn_prefix_bwd_f32(  // >= 2 wav
   }
 }
 
+// ------------------------------------------------------------------ fp32 in / out on the 16-bit MFMA
+// (CLIPK_PREFIX_SPLIT: PREC fp32s). The work decomposition and the math of the MFMA kernels above
+// (one wave per (group, chunk, head), unit 0 the prefix tile, both accumulator layouts in the
+// backward), with every operand element x taken as hi = fp16(x), lo = fp16(x - hi) and every
+// product formed as lo.hi + hi.lo + hi.hi with fp32 accumulation, the three-term rule of the
+// CLIPK_F32S GEMMs. Scaling, mask, max, exp, sums, lse and delta stay fp32.
+// A lane loads its fp32 operand fragment straight into registers: row r16, columns
+// 16 i + 4 g4 .. + 3 (i < 4) -- the four lanes of a row cover 64 contiguous bytes per load
+// instruction. MFMA k-step kk contracts the lane's chunks i = 2 kk, 2 kk + 1; both operands of a
+// product use the same map, so the permuted k order only reorders the sum. The transposed
+// products read fp16 hi / lo tiles (wave-private LDS, stride TRS, true column order). The next
+// unit's rows are loaded once this unit's register operands are dead (after the S / dP products),
+// so they are in flight during the softmax, the transposed products and the stores.
+// The probabilities are split after an exact scale by kPScale: their lo parts are then normal
+// fp16 numbers down to P ~ 2^-15 wherever a conversion flushes subnormals; the accumulator (or the
+// 1 / l factor) undoes it.
+constexpr float kPScale = 4096.0f, kPInv = 1.0f / 4096.0f;
+
+struct Parts8 { s16x8 hi[2], lo[2]; };  // a fragment's k-steps as fp16 hi / lo operands
+
+__device__ __forceinline__ void ld_frag32(const float* p, f32x4 (&x)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) x[i] = *reinterpret_cast<const f32x4*>(p + 16 * i);
+}
+__device__ __forceinline__ void split_frag(const f32x4 (&x)[4], Parts8& o) {
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    f16x8 h, l;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float v = x[2 * kk + j][e];
+        const f16 hh = (f16)v;
+        h[4 * j + e] = hh;
+        l[4 * j + e] = (f16)(v - (float)hh);
+      }
+    o.hi[kk] = __builtin_bit_cast(s16x8, h);
+    o.lo[kk] = __builtin_bit_cast(s16x8, l);
+  }
+}
+// the parts of 4 computed values (split_parts: of the rounded fp32 value)
+__device__ __forceinline__ void split_pack4(float a, float b, float c, float d, s16x4& hi, s16x4& lo) {
+  float x[4] = {a, b, c, d};
+  typedef f16 h4 __attribute__((ext_vector_type(4)));
+  h4 h, l;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    asm volatile("" : "+v"(x[e]));
+    h[e] = (f16)x[e];
+    l[e] = (f16)(x[e] - (float)h[e]);
+  }
+  hi = __builtin_bit_cast(s16x4, h);
+  lo = __builtin_bit_cast(s16x4, l);
+}
+// a fragment's hi / lo parts into the row r16 of two TRS tiles, true column order
+__device__ __forceinline__ void st_parts(const Parts8& f, short* thi, short* tlo, int r16, int g4) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int o = r16 * TRS + 16 * i + 4 * g4;
+    const s16x8 h = f.hi[i >> 1], l = f.lo[i >> 1];
+    const int b = 4 * (i & 1);
+    *reinterpret_cast<s16x4*>(thi + o) = (s16x4){h[b], h[b + 1], h[b + 2], h[b + 3]};
+    *reinterpret_cast<s16x4*>(tlo + o) = (s16x4){l[b], l[b + 1], l[b + 2], l[b + 3]};
+  }
+}
+__device__ __forceinline__ f32x4 mfma32_s3(const Parts8& a, const Parts8& b, f32x4 c) {
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    c = mfma32_t<f16>(a.lo[kk], b.hi[kk], c);
+    c = mfma32_t<f16>(a.hi[kk], b.lo[kk], c);
+  }
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) c = mfma32_t<f16>(a.hi[kk], b.hi[kk], c);
+  return c;
+}
+__device__ __forceinline__ f32x4 mfma16_s3(s16x4 ah, s16x4 al, s16x4 bh, s16x4 bl, f32x4 c) {
+  c = mfma16_t<f16>(al, bh, c);
+  c = mfma16_t<f16>(ah, bl, c);
+  return mfma16_t<f16>(ah, bh, c);
+}
+// prefix row r16's fragment (zero past P)
+__device__ __forceinline__ void ld_prefix_parts(const float* p, bool ok, Parts8& o) {
+  f32x4 x[4];
+  ld_frag32(p, x);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (!ok) x[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  split_frag(x, o);
+}
+// resident waves per CU (VGPRs: forward 150 -> 3 per SIMD, backward <= 256 -> 2; LDS: forward 4,
+// backward 8 tiles of 16 x TRS fp16 per wave = 9 / 18 KiB)
+constexpr int kSplitFwdWpc = 12, kSplitBwdWpc = 8;
+
+template <int WPB>
+__global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_split(
+    int G, int P, int R, int ntiles, const int* __restrict__ tiles, const int* __restrict__ row_first, int H,
+    int nchunk, int uc, const float* __restrict__ qkv, int ldq, float* __restrict__ out, int ldo,
+    float* __restrict__ lse, int cls0) {
+  __shared__ CLIPK_LDS_ALIGN short sm[WPB][4][16 * TRS];  // per wave: prefix V hi, lo; own V hi, lo
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r16 = lane & 15, g4 = lane >> 4;
+  const int wid = blockIdx.x * WPB + w;
+  if (wid >= G * nchunk * H) return;  // wave-uniform; no block barriers below
+  const int h = wid % H, k = (wid / H) % nchunk, g = wid / (H * nchunk);
+  const int W = H * 64;
+  short* sVpH = sm[w][0];
+  short* sVpL = sm[w][1];
+  short* sVoH = sm[w][2];
+  short* sVoL = sm[w][3];
+  const size_t gR = (size_t)g * R;
+  const float* qh = qkv + h * 64 + 4 * g4;
+  const int u_begin = k * uc, u_end = min((k + 1) * uc, ntiles + 1);
+  const int tab = load_tile_table(tiles, ntiles, u_begin, lane);
+
+  f32x4 qn[4], kn[4], vn[4];
+  int firstn = 0;
+  auto fetch = [&](int u) {
+    int t0, n, pre;
+    tile_info(tab, P, u, u_begin, t0, n, pre);
+    const int rl = t0 + min(r16, n - 1);  // clamped: rows past the tile are masked, never zeroed
+    const float* qp = qh + ((cls0 && u > 0 ? 0 : gR) + rl) * ldq;  // cls0: class rows read from group 0
+    ld_frag32(qp, qn);
+    ld_frag32(qp + W, kn);
+    ld_frag32(qp + 2 * W, vn);
+    firstn = u == 0 ? 0 : row_first[rl] - t0;
+  };
+  if (u_begin < u_end) fetch(u_begin);
+  Parts8 kp;
+  {
+    const bool pok = r16 < P;
+    const float* pp = qh + (gR + (pok ? r16 : 0)) * ldq;
+    Parts8 vp;
+    ld_prefix_parts(pp + W, pok, kp);
+    ld_prefix_parts(pp + 2 * W, pok, vp);
+    st_parts(vp, sVpH, sVpL, r16, g4);
+  }
+  for (int u = u_begin; u < u_end; ++u) {
+    int t0, n, pre;
+    tile_info(tab, P, u, u_begin, t0, n, pre);
+    const int first = firstn;
+    const bool qok = r16 < n;
+    Parts8 q, ko;
+    {
+      Parts8 vo;
+      split_frag(qn, q);
+      split_frag(kn, ko);
+      split_frag(vn, vo);
+      lds_fence();  // previous unit's transposed reads of the own-V tiles are done
+      st_parts(vo, sVoH, sVoL, r16, g4);
+    }
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 sp = mfma32_s3(kp, q, z);  // sp[r] = S[query r16][prefix key 4 g4 + r]
+    const f32x4 so = mfma32_s3(ko, q, z);  // so[r] = S[query r16][own key 4 g4 + r]
+    __builtin_amdgcn_sched_barrier(0);
+    if (u + 1 < u_end) fetch(u + 1);
+    float vp[4], vq[4], mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = 4 * g4 + r;
+      vp[r] = key < pre ? sp[r] * kScale : -INFINITY;
+      vq[r] = (key <= r16 && key >= first) ? so[r] * kScale : -INFINITY;  // key == r16 always valid
+      mx = fmaxf(mx, fmaxf(vp[r], vq[r]));
+    }
+    mx = xmax4(mx);
+    float ep[4], eo[4], ps = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      ep[r] = __expf(vp[r] - mx);
+      eo[r] = __expf(vq[r] - mx);
+      ps += ep[r] + eo[r];
+    }
+    ps = xsum4(ps);
+    s16x4 bpH, bpL, boH, boL;
+    split_pack4(ep[0] * kPScale, ep[1] * kPScale, ep[2] * kPScale, ep[3] * kPScale, bpH, bpL);
+    split_pack4(eo[0] * kPScale, eo[1] * kPScale, eo[2] * kPScale, eo[3] * kPScale, boH, boL);
+    const float inv = kPInv / ps;
+    lds_fence();
+    // O^T = V^T P^T (see attn_prefix_fwd_mfma): lane (r16, g4) gets O[query r16][16 t + 4 g4 .. + 3]
+    float* orow = out + (gR + t0 + r16) * ldo + h * 64 + 4 * g4;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      f32x4 o = mfma16_s3(tr_read(sVpH, 4 * g4, 16 * t, lane), tr_read(sVpL, 4 * g4, 16 * t, lane), bpH, bpL, z);
+      o = mfma16_s3(tr_read(sVoH, 4 * g4, 16 * t, lane), tr_read(sVoL, 4 * g4, 16 * t, lane), boH, boL, o);
+      if (qok) *reinterpret_cast<f32x4*>(orow + 16 * t) = o * inv;
+    }
+    if (lse && g4 == 0 && qok) lse[(gR + t0 + r16) * H + h] = mx + __logf(ps);
+  }
+}
+
+// Store a 16-row x 64-column accumulator tile (lane (r16, g4): row r16, columns 16 t + 4 g4 .. + 3
+// in a[t]) as fp32, or (OS) in the pre-split CLIPK_A_SPLIT form: the lanes g4 = 2 j, 2 j + 1 hold
+// the halves of an 8-column group and trade parts over v_permlane16_swap -- the even lane row
+// gets its partner's hi parts, the odd one its partner's lo parts -- so each lane stores one whole
+// 16-B half (even: the group's hi parts, odd: its lo parts). Every lane executes it.
+template <bool OS>
+__device__ __forceinline__ void store_acc64(float* rowp, const f32x4 (&a)[4], float scale, bool ok, int g4) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const f32x4 v = a[t] * scale;
+    if constexpr (!OS) {
+      if (ok) *reinterpret_cast<f32x4*>(rowp + 16 * t + 4 * g4) = v;
+    } else {
+      typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+      s16x4 h, l;
+      split_pack4(v[0], v[1], v[2], v[3], h, l);
+      const u32x2 hu = __builtin_bit_cast(u32x2, h), lu = __builtin_bit_cast(u32x2, l);
+      // swap(h, l): first = {h.row0, l.row0, h.row2, l.row2} (columns 0-3 of the lane's half),
+      // second = {h.row1, l.row1, h.row3, l.row3} (columns 4-7)
+      const auto s0 = __builtin_amdgcn_permlane16_swap(hu[0], lu[0], false, false);
+      const auto s1 = __builtin_amdgcn_permlane16_swap(hu[1], lu[1], false, false);
+      if (ok)
+        reinterpret_cast<u32x4*>(rowp + 16 * t + 8 * (g4 >> 1))[g4 & 1] =
+            (u32x4){(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
+    }
+  }
+}
+
+template <int WPB, bool OS>
+__global__ __launch_bounds__(WPB * 64, 2) void attn_prefix_bwd_split(  // >= 2 waves per SIMD (<= 256 VGPRs)
+    int G, int P, int R, int ntiles, const int* __restrict__ tiles, const int* __restrict__ row_first, int H,
+    int nchunk, int uc, const float* __restrict__ qkv, int ldq, const float* __restrict__ dout, int lddo,
+    const float* __restrict__ lse, float* __restrict__ dqkv, int lddq, float* __restrict__ part, int cls0) {
+  // per wave, hi and lo: K_pre, K_own, Q, dO
+  __shared__ CLIPK_LDS_ALIGN short sm[WPB][8][16 * TRS];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r16 = lane & 15, g4 = lane >> 4;
+  const int wid = blockIdx.x * WPB + w;
+  if (wid >= G * nchunk * H) return;  // wave-uniform
+  const int h = wid % H, k = (wid / H) % nchunk, g = wid / (H * nchunk);
+  const int W = H * 64;
+  short* tKpH = sm[w][0];
+  short* tKpL = sm[w][1];
+  short* tKoH = sm[w][2];
+  short* tKoL = sm[w][3];
+  short* tQH = sm[w][4];
+  short* tQL = sm[w][5];
+  short* tDH = sm[w][6];
+  short* tDL = sm[w][7];
+  const size_t gR = (size_t)g * R;
+  const float* qh = qkv + h * 64 + 4 * g4;
+  const float* dh = dout + h * 64 + 4 * g4;
+  const float* lse_h = lse + h;
+  const int u_begin = k * uc, u_end = min((k + 1) * uc, ntiles + 1);
+  const int tab = load_tile_table(tiles, ntiles, u_begin, lane);
+
+  f32x4 qn[4], kn[4], vn[4], dn[4];
+  float l2n = 0.f;  // row r16's lse and class start; the rows 4 g4 + r get theirs by lane reads
+  int first2n = 0;
+  auto fetch = [&](int u) {
+    int t0, n, pre;
+    tile_info(tab, P, u, u_begin, t0, n, pre);
+    const int rl = t0 + min(r16, n - 1);
+    const float* qp = qh + ((cls0 && u > 0 ? 0 : gR) + rl) * ldq;  // cls0: class rows read from group 0
+    ld_frag32(qp, qn);
+    ld_frag32(qp + W, kn);
+    ld_frag32(qp + 2 * W, vn);
+    ld_frag32(dh + (gR + rl) * lddo, dn);
+    l2n = lse_h[(gR + rl) * H];
+    first2n = u == 0 ? 0 : row_first[rl] - t0;
+  };
+  if (u_begin < u_end) fetch(u_begin);
+  Parts8 kp, vp;
+  {
+    const bool pok = r16 < P;
+    const float* pp = qh + (gR + (pok ? r16 : 0)) * ldq;
+    ld_prefix_parts(pp + W, pok, kp);
+    ld_prefix_parts(pp + 2 * W, pok, vp);
+    st_parts(kp, tKpH, tKpL, r16, g4);
+  }
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  f32x4 dkp[4], dvp[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    dkp[t] = z;
+    dvp[t] = z;
+  }
+  for (int u = u_begin; u < u_end; ++u) {
+    int t0, n, pre;
+    tile_info(tab, P, u, u_begin, t0, n, pre);
+    const bool own_is_prefix = u == 0;
+    const bool qok = r16 < n;
+    const float l2 = l2n;
+    const int first2 = first2n;
+    f32x4 s1p, s2p, p1p, p2p, s1o, s2o, p1o, p2o;
+    {
+      Parts8 q, ko, vo, d;
+      split_frag(qn, q);
+      split_frag(kn, ko);
+      split_frag(vn, vo);
+      split_frag(dn, d);
+      lds_fence();  // previous unit's transposed reads are done
+      st_parts(q, tQH, tQL, r16, g4);
+      st_parts(ko, tKoH, tKoL, r16, g4);
+      st_parts(d, tDH, tDL, r16, g4);
+      s1p = mfma32_s3(q, kp, z);   // S  [i = 4 g4 + r][j = r16]
+      s2p = mfma32_s3(kp, q, z);   // S^T[j = 4 g4 + r][i = r16]
+      p1p = mfma32_s3(d, vp, z);   // dP [i][j]
+      p2p = mfma32_s3(vp, d, z);   // dP^T
+      s1o = mfma32_s3(q, ko, z);
+      s2o = mfma32_s3(ko, q, z);
+      p1o = mfma32_s3(d, vo, z);
+      p2o = mfma32_s3(vo, d, z);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (u + 1 < u_end) fetch(u + 1);
+    // layout 2: i = r16, j = 4 g4 + r  (rows past the tile are clamped copies: masked, not zeroed)
+    float P2p[4], P2o[4], Dsum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int j = 4 * g4 + r;
+      P2p[r] = (qok && j < pre) ? __expf(s2p[r] * kScale - l2) : 0.f;
+      P2o[r] = (qok && j <= r16 && j >= first2) ? __expf(s2o[r] * kScale - l2) : 0.f;
+      Dsum += P2p[r] * p2p[r] + P2o[r] * p2o[r];
+    }
+    Dsum = xsum4(Dsum);  // delta_i = sum_j P_ij dP_ij for i = r16 (the forward output is not read)
+    s16x4 bTpH, bTpL, bToH, bToL;  // dS^T: B[k = j][n = i]
+    split_pack4(P2p[0] * (p2p[0] - Dsum), P2p[1] * (p2p[1] - Dsum), P2p[2] * (p2p[2] - Dsum),
+                P2p[3] * (p2p[3] - Dsum), bTpH, bTpL);
+    split_pack4(P2o[0] * (p2o[0] - Dsum), P2o[1] * (p2o[1] - Dsum), P2o[2] * (p2o[2] - Dsum),
+                P2o[3] * (p2o[3] - Dsum), bToH, bToL);
+    // layout 1: i = 4 g4 + r, j = r16
+    float P1p[4], P1o[4], dS1p[4], dS1o[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = 4 * g4 + r;
+      const bool iok = i < n;
+      const float Di = __shfl(Dsum, i, 64), l1 = __shfl(l2, i, 64);
+      const int first1 = __shfl(first2, i, 64);
+      P1p[r] = (iok && r16 < pre) ? __expf(s1p[r] * kScale - l1) : 0.f;
+      P1o[r] = (iok && r16 <= i && r16 >= first1) ? __expf(s1o[r] * kScale - l1) : 0.f;
+      dS1p[r] = P1p[r] * (p1p[r] - Di);
+      dS1o[r] = P1o[r] * (p1o[r] - Di);
+    }
+    s16x4 bPpH, bPpL, bPoH, bPoL, bSpH, bSpL, bSoH, bSoL;  // B[k = i][n = j]
+    split_pack4(P1p[0] * kPScale, P1p[1] * kPScale, P1p[2] * kPScale, P1p[3] * kPScale, bPpH, bPpL);
+    split_pack4(P1o[0] * kPScale, P1o[1] * kPScale, P1o[2] * kPScale, P1o[3] * kPScale, bPoH, bPoL);
+    split_pack4(dS1p[0], dS1p[1], dS1p[2], dS1p[3], bSpH, bSpL);
+    split_pack4(dS1o[0], dS1o[1], dS1o[2], dS1o[3], bSoH, bSoL);
+    lds_fence();
+    // one output (16 rows x 64) at a time, so only one 16-register tile is live for the store
+    float* orow = dqkv + (gR + t0 + r16) * lddq + h * 64;
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      acc[t] = mfma16_s3(tr_read(tKpH, 4 * g4, 16 * t, lane), tr_read(tKpL, 4 * g4, 16 * t, lane), bTpH, bTpL, z);
+      acc[t] = mfma16_s3(tr_read(tKoH, 4 * g4, 16 * t, lane), tr_read(tKoL, 4 * g4, 16 * t, lane), bToH, bToL, acc[t]);
+    }
+    store_acc64<OS>(orow, acc, kScale, qok, g4);  // dQ
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const s16x4 aH = tr_read(tQH, 4 * g4, 16 * t, lane), aL = tr_read(tQL, 4 * g4, 16 * t, lane);
+      dkp[t] = mfma16_s3(aH, aL, bSpH, bSpL, dkp[t]);
+      acc[t] = mfma16_s3(aH, aL, bSoH, bSoL, z);
+      if (own_is_prefix) dkp[t] += acc[t];  // the prefix tile's keys are the prefix rows themselves
+    }
+    if (!own_is_prefix) store_acc64<OS>(orow + W, acc, kScale, qok, g4);  // dK (wave-uniform branch)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const s16x4 aH = tr_read(tDH, 4 * g4, 16 * t, lane), aL = tr_read(tDL, 4 * g4, 16 * t, lane);
+      dvp[t] = mfma16_s3(aH, aL, bPpH, bPpL, dvp[t]);
+      acc[t] = mfma16_s3(aH, aL, bPoH, bPoL, z);
+      if (own_is_prefix) dvp[t] += acc[t];
+    }
+    if (!own_is_prefix) store_acc64<OS>(orow + 2 * W, acc, kPInv, qok, g4);  // dV
+  }
+  // this chunk's partial dK/dV of the prefix rows (fp32, [G][nchunk][16][2W])
+  float* pb = part + ((size_t)g * nchunk + k) * 16 * (2 * W);
+  if (r16 < P) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      float* dst = pb + (size_t)r16 * 2 * W + h * 64 + 16 * t + 4 * g4;
+      *reinterpret_cast<f32x4*>(dst) = dkp[t] * kScale;
+      *reinterpret_cast<f32x4*>(dst + W) = dvp[t] * kPInv;
+    }
+  }
+}
+
 // prefix rows' dK | dV = sum over chunks of the partials (fixed order)
 template <typename TG>
 __global__ __launch_bounds__(256) void prefix_kv_reduce(int P, int R, int W, int nchunk,
@@ -1286,6 +1665,45 @@ static int prefix_bwd(int G, int P, int R, int ntiles, const int* tiles, const i
   return CLIPK_OK;
 }
 
+// CLIPK_PREFIX_SPLIT: the fp32 tensors on the 16-bit MFMA (attn_prefix_*_split). The backward's
+// chunking is the fp32 VALU backward's (kSplitBwdWpc == kF32BwdWpc), so
+// clipk_attention_prefix_ws_bytes covers its partials; the forward output is not read.
+static int prefix_fwd_split(int G, int P, int R, int ntiles, const int* tiles, const int* row_first, int H,
+                            const void* qkv, int ldq, void* out, int ldo, float* lse, hipStream_t st, int cls0) {
+  constexpr int WPB = 4;
+  const int uc = f32_uc(G, ntiles, H, kSplitFwdWpc);
+  const int nchunk = n_chunks(ntiles, uc);
+  const long waves = (long)G * nchunk * H;
+  hipLaunchKernelGGL(attn_prefix_fwd_split<WPB>, dim3((waves + WPB - 1) / WPB), dim3(64 * WPB), 0, st, G, P, R, ntiles,
+                     tiles, row_first, H, nchunk, uc, (const float*)qkv, ldq, (float*)out, ldo, lse, cls0);
+  CLIPK_CHECK_LAUNCH();
+  return CLIPK_OK;
+}
+
+template <bool OS>
+static int prefix_bwd_split(int G, int P, int R, int ntiles, const int* tiles, const int* row_first, int H,
+                            const void* qkv, int ldq, const void* dout, int lddo, const float* lse, void* dqkv,
+                            int lddq, float* part, hipStream_t st, int cls0) {
+  static_assert(kSplitBwdWpc == kF32BwdWpc, "workspace sized by the fp32 backward's chunking");
+  constexpr int WPB = 2;
+  const int uc = f32_uc(G, ntiles, H, kSplitBwdWpc);
+  const int nchunk = n_chunks(ntiles, uc);
+  const long waves = (long)G * nchunk * H;
+  hipLaunchKernelGGL((attn_prefix_bwd_split<WPB, OS>), dim3((waves + WPB - 1) / WPB), dim3(64 * WPB), 0, st, G, P, R,
+                     ntiles, tiles, row_first, H, nchunk, uc, (const float*)qkv, ldq, (const float*)dout, lddo, lse,
+                     (float*)dqkv, lddq, part, cls0);
+  CLIPK_CHECK_LAUNCH();
+  const int W = H * 64;
+  if constexpr (OS)
+    hipLaunchKernelGGL(prefix_kv_reduce_split, dim3(G * P, (2 * W + 255) / 256), dim3(256), 0, st, P, R, W,
+                       nchunk, part, (float*)dqkv, lddq);
+  else
+    hipLaunchKernelGGL((prefix_kv_reduce<float>), dim3(G * P, (2 * W + 255) / 256), dim3(256), 0, st, P, R, W,
+                       nchunk, part, (float*)dqkv, lddq);
+  CLIPK_CHECK_LAUNCH();
+  return CLIPK_OK;
+}
+
 }  // namespace clipk
 
 using namespace clipk;
@@ -1304,17 +1722,23 @@ extern "C" size_t clipk_attention_prefix_ws_bytes(int G, int ntiles, int heads) 
 
 // flags (the _ex entry points): CLIPK_PREFIX_CLS_GROUP0 -- the class rows' q|k|v are read from
 // group 0 for every group (the text encoder's layer 0, whose class rows are the same in every
-// group: no per-group copies of them are materialised); prefix rows and every output per group
+// group: no per-group copies of them are materialised); prefix rows and every output per group.
+// CLIPK_PREFIX_SPLIT -- fp32 tensors only: the products as fp16 hi / lo parts on the 16-bit MFMA
+// (attn_prefix_*_split) instead of the exact-fp32 VALU kernels
+constexpr int kPrefixFlags = CLIPK_PREFIX_CLS_GROUP0 | CLIPK_PREFIX_SPLIT;
 static int prefix_fwd_call(int dtype, int G, int P, int R, int ntiles, const int* tiles, const int* row_first,
                            int heads, const void* qkv, int ldqkv, void* out, int ldo, float* lse, int flags,
                            void* stream) {
   if (!tiles || !row_first || !qkv || !out) return CLIPK_EINVAL;
-  if (flags & ~CLIPK_PREFIX_CLS_GROUP0) return CLIPK_EINVAL;
+  if (flags & ~kPrefixFlags) return CLIPK_EINVAL;
+  if ((flags & CLIPK_PREFIX_SPLIT) && dtype != CLIPK_F32) return CLIPK_EINVAL;
   if (!prefix_shape_ok(G, P, R, ntiles, heads, ldqkv) || ldqkv < 3 * heads * 64 || ldo < heads * 64 ||
       ldqkv % 8 || ldo % 8)
     return CLIPK_ESHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int c0 = (flags & CLIPK_PREFIX_CLS_GROUP0) ? 1 : 0;
+  if (flags & CLIPK_PREFIX_SPLIT)
+    return prefix_fwd_split(G, P, R, ntiles, tiles, row_first, heads, qkv, ldqkv, out, ldo, lse, st, c0);
   switch (dtype) {
     case CLIPK_F16: return prefix_fwd<f16>(G, P, R, ntiles, tiles, row_first, heads, qkv, ldqkv, out, ldo, lse, st, c0);
     case CLIPK_BF16: return prefix_fwd<bf16>(G, P, R, ntiles, tiles, row_first, heads, qkv, ldqkv, out, ldo, lse, st, c0);
@@ -1340,7 +1764,9 @@ static int prefix_bwd_call(int dtype, int grad_dtype, int G, int P, int R, int n
                            const void* dout, int lddo, const float* lse, void* dqkv, int lddqkv, void* ws,
                            size_t ws_bytes, int flags, void* stream) {
   if (!tiles || !row_first || !qkv || !ofwd || !dout || !lse || !dqkv || !ws) return CLIPK_EINVAL;
-  if (flags & ~CLIPK_PREFIX_CLS_GROUP0) return CLIPK_EINVAL;
+  if (flags & ~kPrefixFlags) return CLIPK_EINVAL;
+  if ((flags & CLIPK_PREFIX_SPLIT) && (dtype != CLIPK_F32 || (grad_dtype != CLIPK_F32 && grad_dtype != CLIPK_F32S)))
+    return CLIPK_EINVAL;
   if (!prefix_shape_ok(G, P, R, ntiles, heads, lddqkv) || ldqkv < 3 * heads * 64 || lddqkv < 3 * heads * 64 ||
       ldof < heads * 64 || lddo < heads * 64)
     return CLIPK_ESHAPE;
@@ -1348,7 +1774,17 @@ static int prefix_bwd_call(int dtype, int grad_dtype, int G, int P, int R, int n
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)ws;
   const int c0 = (flags & CLIPK_PREFIX_CLS_GROUP0) ? 1 : 0;
-#define CLIPK_PBWD(TT, TGG)                                                                            \
+  if (flags & CLIPK_PREFIX_SPLIT) {
+    if (ldqkv % 4 || lddo % 4 || lddqkv % 4) return CLIPK_ESHAPE;  // 16-B loads and stores
+    if (grad_dtype == CLIPK_F32S) {
+      if (lddqkv % 8) return CLIPK_ESHAPE;  // whole 8-column groups per row
+      return prefix_bwd_split<true>(G, P, R, ntiles, tiles, row_first, heads, qkv, ldqkv, dout, lddo, lse, dqkv,
+                                    lddqkv, part, st, c0);
+    }
+    return prefix_bwd_split<false>(G, P, R, ntiles, tiles, row_first, heads, qkv, ldqkv, dout, lddo, lse, dqkv,
+                                   lddqkv, part, st, c0);
+  }
+#define CLIPK_PBWD(TT, TGG)                                                                           \
   return prefix_bwd<TT, TGG>(G, P, R, ntiles, tiles, row_first, heads, qkv, ldqkv, ofwd, ldof, dout, lddo, \
                              lse, dqkv, lddqkv, part, st, c0)
   if (dtype == CLIPK_F16 && grad_dtype == CLIPK_BF16) CLIPK_PBWD(f16, bf16);

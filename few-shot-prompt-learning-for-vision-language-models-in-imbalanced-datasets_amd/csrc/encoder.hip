@@ -383,13 +383,29 @@ struct SeqShape {
   size_t part_bytes(int heads) const { return packed ? clipk_attention_prefix_ws_bytes(G, ntiles, heads) : 0; }
 };
 
+// PREC fp32s on the packed text rows: the prefix attention's products run on the 16-bit MFMA as
+// fp16 hi / lo parts (CLIPK_PREFIX_SPLIT), as every GEMM of the mode does. A part beyond fp16's
+// range gives inf / NaN outputs, which split_check / the status bits catch downstream. Each
+// direction is on only where its split kernel measured faster than the fp32 VALU one.
+// Knob CLIPK_PREFIX_SPLIT_ATTN (bit 0 forward, bit 1 backward; default both; read at every call,
+// so one process can run both paths): 0 = the exact-fp32 VALU kernels.
+constexpr int kPrefixSplitFwd = 1, kPrefixSplitBwd = 2, kPrefixSplitDefault = kPrefixSplitFwd | kPrefixSplitBwd;
+static int prefix_split_flag(const clipk_encoder* e, int dir) {
+  const char* s = getenv("CLIPK_PREFIX_SPLIT_ATTN");
+  const int on = s ? atoi(s) : kPrefixSplitDefault;
+  return (on & dir) && e->split != 0 && e->act == CLIPK_F32 ? CLIPK_PREFIX_SPLIT : 0;
+}
+static bool prefix_split_bwd(const clipk_encoder* e, const SeqShape& sh, int gd) {
+  return sh.packed && gd == CLIPK_F32 && prefix_split_flag(e, kPrefixSplitBwd) != 0;
+}
+
 // pflags: clipk_attention_prefix_*_ex flags (CLIPK_PREFIX_CLS_GROUP0: layer 0 under forward sharing)
 static int attn_fwd(const clipk_encoder* e, const SeqShape& sh, const void* qkv, void* o, float* lse,
                     hipStream_t st, int pflags = 0) {
   const int W = e->W;
   if (sh.packed)
     return clipk_attention_prefix_fwd_ex(e->act, sh.G, sh.P, sh.R, sh.ntiles, sh.tiles, sh.row_first, e->heads,
-                                         qkv, 3 * W, o, W, lse, pflags, st);
+                                         qkv, 3 * W, o, W, lse, pflags | prefix_split_flag(e, kPrefixSplitFwd), st);
   return clipk_attention_fwd(e->act, sh.nseq, sh.L, e->heads, sh.causal, qkv, 3 * W, o, W, lse, st);
 }
 
@@ -402,7 +418,8 @@ static int attn_bwd(const clipk_encoder* e, const SeqShape& sh, const void* qkv,
   if (sh.packed)
     return clipk_attention_prefix_bwd_ex(e->act, dqkv_split ? CLIPK_F32S : e->grad, sh.G, sh.P, sh.R, sh.ntiles, sh.tiles, sh.row_first,
                                       e->heads, qkv, 3 * W, o, W, dout, W, lse, dqkv, 3 * W, part,
-                                      sh.part_bytes(e->heads), pflags, st);
+                                      sh.part_bytes(e->heads),
+                                      pflags | (prefix_split_bwd(e, sh, e->grad) ? CLIPK_PREFIX_SPLIT : 0), st);
   return clipk_attention_bwd(e->act, e->grad, sh.nseq, sh.L, e->heads, sh.causal, qkv, 3 * W, o, W, dout, W,
                              lse, dqkv, 3 * W, st);
 }
@@ -1031,8 +1048,9 @@ static int text_backward_impl(const clipk_encoder* e, const SeqShape& sh, const 
     }
     {
       // algorithmic: read q|k|v (act), do (grad), lse; write dq|dk|dv (grad); the fp32 VALU
-      // kernels also read o (the 16-bit MFMA ones recompute D_i = rowsum(P o dP) instead)
-      const double ab = (double)rows * W * ((act == CLIPK_F32 ? 4.0 : 3.0) * esize(act) + 4.0 * esize(gd)) +
+      // kernels also read o (the MFMA ones, 16-bit and split fp32, recompute D_i = rowsum(P o dP))
+      const bool reads_o = act == CLIPK_F32 && !prefix_split_bwd(e, sh, gd);
+      const double ab = (double)rows * W * ((reads_o ? 4.0 : 3.0) * esize(act) + 4.0 * esize(gd)) +
                         4.0 * rows * e->heads;
       ProfScope ps(io.text ? CLIPK_PROF_ATTN : CLIPK_PROF_NONE, st, 0.0, SITE("attn_bwd"), ab);
       // layer 0 under forward sharing: its class rows of q|k|v exist in group 0 only

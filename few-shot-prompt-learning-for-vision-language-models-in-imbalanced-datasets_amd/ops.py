@@ -332,7 +332,8 @@ def ctx_grad_rows(G, R, W, n_ctx, slot_ptr, slot_rows, dx0):
 def attention_prefix(qkv, G, P, R, tiles, row_first, heads, lse=False, flags=0):
     """Shared-prefix packed causal attention (clipk_attention_prefix_fwd_ex); tiles int32
     [ntiles*2] (first row, rows), row_first int32 [R]; flags N.PREFIX_CLS_GROUP0: class rows'
-    q|k|v read from group 0."""
+    q|k|v read from group 0; N.PREFIX_SPLIT (fp32 qkv only): the products on the 16-bit MFMA as
+    fp16 hi / lo parts."""
     _need(qkv, "qkv")
     _need(tiles, "tiles", torch.int32)
     _need(row_first, "row_first", torch.int32)
@@ -346,7 +347,8 @@ def attention_prefix(qkv, G, P, R, tiles, row_first, heads, lse=False, flags=0):
 
 def attention_prefix_bwd(qkv, o, dout, lse, G, P, R, tiles, row_first, heads, grad_dtype, split=False, flags=0):
     """split (fp32 qkv / dout / grad_dtype): dq|dk|dv in the pre-split operand form of CLIPK_A_SPLIT
-    (grad dtype CLIPK_F32S), viewed as fp32 [G*R, 3W]."""
+    (grad dtype CLIPK_F32S), viewed as fp32 [G*R, 3W]. flags as attention_prefix; with
+    N.PREFIX_SPLIT (fp32 tensors only) `o` is not read."""
     W = heads * 64
     nt = tiles.numel() // 2
     dqkv = torch.zeros(G * R, 3 * W, device=qkv.device, dtype=grad_dtype)

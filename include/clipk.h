@@ -316,8 +316,15 @@ int clipk_attention_prefix_bwd(int dtype, int grad_dtype, int G, int P, int R, i
 /* The same with flags: CLIPK_PREFIX_CLS_GROUP0 -- every group's class rows read their q|k|v from
  * group 0's rows (the text encoder's layer 0, where the class rows enter every group with the
  * same values: clipk_encoder_set_input_rows; rows [P, R) of groups >= 1 of qkv are then never
- * read, so no copies of group 0's are written). Prefix rows, outputs, dout, lse per group. */
-enum { CLIPK_PREFIX_CLS_GROUP0 = 1 };
+ * read, so no copies of group 0's are written). Prefix rows, outputs, dout, lse per group.
+ * CLIPK_PREFIX_SPLIT -- fp32 tensors on the 16-bit MFMA (PREC fp32s): every operand element x is
+ * taken as hi = fp16(x), lo = fp16(x - hi) and every product (Q.K^T, P.V; in the backward dO.V^T,
+ * dS.K, dS^T.Q, P^T.dO) as hi.hi + hi.lo + lo.hi with fp32 accumulation, the three-term rule of
+ * CLIPK_F32S; softmax, lse and delta = sum_j P.dP stay fp32. Valid only with dtype CLIPK_F32 (the
+ * backward: grad_dtype CLIPK_F32 or CLIPK_F32S), otherwise CLIPK_EINVAL; combines with
+ * CLIPK_PREFIX_CLS_GROUP0. The backward accepts ofwd and does not read it. A part beyond fp16's
+ * range gives inf / NaN outputs. Without the flag the fp32 calls run the exact-fp32 kernels. */
+enum { CLIPK_PREFIX_CLS_GROUP0 = 1, CLIPK_PREFIX_SPLIT = 2 };
 int clipk_attention_prefix_fwd_ex(int dtype, int G, int P, int R, int ntiles, const int* tiles,
                                   const int* row_first, int heads, const void* qkv, int ldqkv, void* out,
                                   int ldo, float* lse, int flags, void* stream);

@@ -4,6 +4,7 @@ setting (the CLIPK_PREFIX_* knobs are read once per process).
 
     python tools/attn_sweep.py            # sweep (spawns one child per setting)
     python tools/attn_sweep.py --one      # time the current environment's setting
+                                          # (SWEEP_DTYPE=fp16 | fp32 | fp32s, SWEEP_CACHE)
     python tools/attn_sweep.py --anyl     # the fp32 any-L forward (attn_fwd_f32): ViT-B/16
                                           # L = 197 (100 images) and plain text L = 77 (causal)
 """
@@ -32,8 +33,12 @@ def one(iters=30):
     tiles = torch.from_numpy(tl.reshape(-1).copy()).to(dev)
     row_first = torch.from_numpy(rf).to(dev)
     nt = tiles.numel() // 2
-    # SWEEP_DTYPE=fp32: the fp32 kernels (PREC fp32 / fp32s), which also read the forward output
-    f32 = os.environ.get("SWEEP_DTYPE", "fp16") == "fp32"
+    # SWEEP_DTYPE=fp32: the exact-fp32 VALU kernels (PREC fp32), which also read the forward output;
+    # fp32s: the same fp32 tensors with CLIPK_PREFIX_SPLIT (the 16-bit MFMA on fp16 hi / lo parts,
+    # PREC fp32s), which do not
+    sdt = os.environ.get("SWEEP_DTYPE", "fp16")
+    f32, split = sdt in ("fp32", "fp32s"), sdt == "fp32s"
+    flags = N.PREFIX_SPLIT if split else 0
     dt, did, esz = (torch.float32, N.F32, 4) if f32 else (torch.float16, N.F16, 2)
     qkv = (torch.randn(G * R, 3 * W, device=dev) * 0.5).to(dt)
     dout = (torch.randn(G * R, W, device=dev) * 0.5).to(dt)
@@ -47,20 +52,20 @@ def one(iters=30):
     p = lambda t: ctypes.c_void_p(t.data_ptr())
     st = torch.cuda.current_stream()
     sp = ctypes.c_void_p(st.cuda_stream)
-    o, lse = ops.attention_prefix(qkv, G, P, R, tiles, row_first, H, lse=True)
+    o, lse = ops.attention_prefix(qkv, G, P, R, tiles, row_first, H, lse=True, flags=flags)
 
     def bwd():
-        N.call("clipk_attention_prefix_bwd", did, did, G, P, R, nt, p(tiles), p(row_first), H, p(qkv),
-               3 * W, p(o), W, p(dout), W, p(lse), p(dq), 3 * W, p(ws), nb, sp)
+        N.call("clipk_attention_prefix_bwd_ex", did, did, G, P, R, nt, p(tiles), p(row_first), H, p(qkv),
+               3 * W, p(o), W, p(dout), W, p(lse), p(dq), 3 * W, p(ws), nb, flags, sp)
 
     def fwd():
-        N.call("clipk_attention_prefix_fwd", did, G, P, R, nt, p(tiles), p(row_first), H, p(qkv), 3 * W,
-               p(o), W, p(lse), sp)
+        N.call("clipk_attention_prefix_fwd_ex", did, G, P, R, nt, p(tiles), p(row_first), H, p(qkv), 3 * W,
+               p(o), W, p(lse), flags, sp)
 
     rows = G * R
     res = {"rows": rows, "tiles_per_group": nt}
     for name, fn, by in (("fwd", fwd, rows * W * 4 * esz + 4 * rows * H),
-                         ("bwd", bwd, rows * W * (9 if f32 else 8) * esz + 4 * rows * H)):
+                         ("bwd", bwd, rows * W * (9 if f32 and not split else 8) * esz + 4 * rows * H)):
         ts = []
         for i in range(iters + 3):
             if mode == "clean":

@@ -23,8 +23,13 @@ def kernel_regs(obj):
         notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True,
                                text=True).stdout
     rows = []
-    for e in notes.split(".name:")[1:]:
-        name = e.split("\n")[0].strip()
+    # one list item per kernel; its keys are sorted, so .agpr_count / .group_segment_fixed_size
+    # stand BEFORE .name (splitting at .name would take them from the next kernel)
+    for e in re.split(r"\n\s*- (?=\.agpr_count:)", notes)[1:]:
+        m = re.search(r"\.name:\s+(\S+)", e)
+        if not m:
+            continue
+        name = m.group(1)
 
         def g(k):
             m = re.search(r"\." + k + r":\s+(\d+)", e)
