@@ -37,6 +37,7 @@ def source_digest():
 F32, F16, BF16, F32S = 0, 1, 2, 3  # F32S: fp32 activations x split-packed weights (PREC fp32s)
 PREFIX_CLS_GROUP0 = 1  # clipk_attention_prefix_*_ex flag
 PREFIX_SPLIT = 2  # ... fp32 tensors on the 16-bit MFMA as fp16 hi / lo parts (PREC fp32s)
+PREFIX_OUT_SPLIT = 4  # ... forward, with PREFIX_SPLIT: o stored pre-split (the form of A_SPLIT) for out_proj
 F32S16 = 4  # F32S for fp16-valued weights: B is the compact fp16 SPLIT_SCALE * W (clipk_split_hi16)
 SPLIT_SCALE = 64.0  # CLIPK_SPLIT_SCALE: clipk_split_pack stores SPLIT_SCALE * W
 EPI_BIAS, EPI_BIAS_RES, EPI_BIAS_QGELU, EPI_DQGELU, EPI_NONE = 0, 1, 2, 3, 4
@@ -71,6 +72,8 @@ SIGNATURES = {
     "clipk_gemm_ln": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "clipk_ln_stats_merge": (_I, [_I, _I, _P, _P, _P, _P, _P]),
     "clipk_gemm_ln_merge_fused": (_I, [_I, _I, _I, _I]),
+    "clipk_gemm_split_tile_rows": (_I, [_I, _I, _I, _I, _I]),
+    "clipk_gemm_t256_cost": (_D, [_I, _I, _I]),
     "clipk_gemm_ln_stats_split": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
     "clipk_gemm_ln_gamma": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     "clipk_gemm_ln_merge": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),

@@ -1183,11 +1183,42 @@ __device__ __forceinline__ void ld_prefix_parts(const float* p, bool ok, Parts8&
     if (!ok) x[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
   split_frag(x, o);
 }
+// Store a 16-row x 64-column accumulator tile (lane (r16, g4): row r16, columns 16 t + 4 g4 .. + 3
+// in a[t]) as fp32, or (OS) in the pre-split CLIPK_A_SPLIT form: the lanes g4 = 2 j, 2 j + 1 hold
+// the halves of an 8-column group and trade parts over v_permlane16_swap -- the even lane row
+// gets its partner's hi parts, the odd one its partner's lo parts -- so each lane stores one whole
+// 16-B half (even: the group's hi parts, odd: its lo parts). Every lane executes it.
+// store_acc16: one 16-column chunk t (v the lane's 4 values of it); rowp the row's column 0.
+template <bool OS>
+__device__ __forceinline__ void store_acc16(float* rowp, const f32x4 v, int t, bool ok, int g4) {
+  if constexpr (!OS) {
+    if (ok) *reinterpret_cast<f32x4*>(rowp + 16 * t + 4 * g4) = v;
+  } else {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    s16x4 h, l;
+    split_pack4(v[0], v[1], v[2], v[3], h, l);
+    const u32x2 hu = __builtin_bit_cast(u32x2, h), lu = __builtin_bit_cast(u32x2, l);
+    // swap(h, l): first = {h.row0, l.row0, h.row2, l.row2} (columns 0-3 of the lane's half),
+    // second = {h.row1, l.row1, h.row3, l.row3} (columns 4-7)
+    const auto s0 = __builtin_amdgcn_permlane16_swap(hu[0], lu[0], false, false);
+    const auto s1 = __builtin_amdgcn_permlane16_swap(hu[1], lu[1], false, false);
+    if (ok)
+      reinterpret_cast<u32x4*>(rowp + 16 * t + 8 * (g4 >> 1))[g4 & 1] =
+          (u32x4){(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
+  }
+}
+template <bool OS>
+__device__ __forceinline__ void store_acc64(float* rowp, const f32x4 (&a)[4], float scale, bool ok, int g4) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) store_acc16<OS>(rowp, a[t] * scale, t, ok, g4);
+}
+
 // resident waves per CU (VGPRs: forward 150 -> 3 per SIMD, backward <= 256 -> 2; LDS: forward 4,
 // backward 8 tiles of 16 x TRS fp16 per wave = 9 / 18 KiB)
 constexpr int kSplitFwdWpc = 12, kSplitBwdWpc = 8;
 
-template <int WPB>
+// OS (CLIPK_PREFIX_OUT_SPLIT): o stored in the pre-split CLIPK_A_SPLIT form, the parts of the fp32 o
+template <int WPB, bool OS>
 __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_split(
     int G, int P, int R, int ntiles, const int* __restrict__ tiles, const int* __restrict__ row_first, int H,
     int nchunk, int uc, const float* __restrict__ qkv, int ldq, float* __restrict__ out, int ldo,
@@ -1272,42 +1303,14 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_split(
     const float inv = kPInv / ps;
     lds_fence();
     // O^T = V^T P^T (see attn_prefix_fwd_mfma): lane (r16, g4) gets O[query r16][16 t + 4 g4 .. + 3]
-    float* orow = out + (gR + t0 + r16) * ldo + h * 64 + 4 * g4;
+    float* orow = out + (gR + t0 + r16) * ldo + h * 64;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       f32x4 o = mfma16_s3(tr_read(sVpH, 4 * g4, 16 * t, lane), tr_read(sVpL, 4 * g4, 16 * t, lane), bpH, bpL, z);
       o = mfma16_s3(tr_read(sVoH, 4 * g4, 16 * t, lane), tr_read(sVoL, 4 * g4, 16 * t, lane), boH, boL, o);
-      if (qok) *reinterpret_cast<f32x4*>(orow + 16 * t) = o * inv;
+      store_acc16<OS>(orow, o * inv, t, qok, g4);
     }
     if (lse && g4 == 0 && qok) lse[(gR + t0 + r16) * H + h] = mx + __logf(ps);
-  }
-}
-
-// Store a 16-row x 64-column accumulator tile (lane (r16, g4): row r16, columns 16 t + 4 g4 .. + 3
-// in a[t]) as fp32, or (OS) in the pre-split CLIPK_A_SPLIT form: the lanes g4 = 2 j, 2 j + 1 hold
-// the halves of an 8-column group and trade parts over v_permlane16_swap -- the even lane row
-// gets its partner's hi parts, the odd one its partner's lo parts -- so each lane stores one whole
-// 16-B half (even: the group's hi parts, odd: its lo parts). Every lane executes it.
-template <bool OS>
-__device__ __forceinline__ void store_acc64(float* rowp, const f32x4 (&a)[4], float scale, bool ok, int g4) {
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const f32x4 v = a[t] * scale;
-    if constexpr (!OS) {
-      if (ok) *reinterpret_cast<f32x4*>(rowp + 16 * t + 4 * g4) = v;
-    } else {
-      typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-      s16x4 h, l;
-      split_pack4(v[0], v[1], v[2], v[3], h, l);
-      const u32x2 hu = __builtin_bit_cast(u32x2, h), lu = __builtin_bit_cast(u32x2, l);
-      // swap(h, l): first = {h.row0, l.row0, h.row2, l.row2} (columns 0-3 of the lane's half),
-      // second = {h.row1, l.row1, h.row3, l.row3} (columns 4-7)
-      const auto s0 = __builtin_amdgcn_permlane16_swap(hu[0], lu[0], false, false);
-      const auto s1 = __builtin_amdgcn_permlane16_swap(hu[1], lu[1], false, false);
-      if (ok)
-        reinterpret_cast<u32x4*>(rowp + 16 * t + 8 * (g4 >> 1))[g4 & 1] =
-            (u32x4){(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
-    }
   }
 }
 
@@ -1669,13 +1672,18 @@ static int prefix_bwd(int G, int P, int R, int ntiles, const int* tiles, const i
 // chunking is the fp32 VALU backward's (kSplitBwdWpc == kF32BwdWpc), so
 // clipk_attention_prefix_ws_bytes covers its partials; the forward output is not read.
 static int prefix_fwd_split(int G, int P, int R, int ntiles, const int* tiles, const int* row_first, int H,
-                            const void* qkv, int ldq, void* out, int ldo, float* lse, hipStream_t st, int cls0) {
+                            const void* qkv, int ldq, void* out, int ldo, float* lse, hipStream_t st, int cls0,
+                            bool out_split) {
   constexpr int WPB = 4;
   const int uc = f32_uc(G, ntiles, H, kSplitFwdWpc);
   const int nchunk = n_chunks(ntiles, uc);
   const long waves = (long)G * nchunk * H;
-  hipLaunchKernelGGL(attn_prefix_fwd_split<WPB>, dim3((waves + WPB - 1) / WPB), dim3(64 * WPB), 0, st, G, P, R, ntiles,
-                     tiles, row_first, H, nchunk, uc, (const float*)qkv, ldq, (float*)out, ldo, lse, cls0);
+  if (out_split)
+    hipLaunchKernelGGL((attn_prefix_fwd_split<WPB, true>), dim3((waves + WPB - 1) / WPB), dim3(64 * WPB), 0, st, G, P, R,
+                       ntiles, tiles, row_first, H, nchunk, uc, (const float*)qkv, ldq, (float*)out, ldo, lse, cls0);
+  else
+    hipLaunchKernelGGL((attn_prefix_fwd_split<WPB, false>), dim3((waves + WPB - 1) / WPB), dim3(64 * WPB), 0, st, G, P, R,
+                       ntiles, tiles, row_first, H, nchunk, uc, (const float*)qkv, ldq, (float*)out, ldo, lse, cls0);
   CLIPK_CHECK_LAUNCH();
   return CLIPK_OK;
 }
@@ -1725,20 +1733,26 @@ extern "C" size_t clipk_attention_prefix_ws_bytes(int G, int ntiles, int heads) 
 // group: no per-group copies of them are materialised); prefix rows and every output per group.
 // CLIPK_PREFIX_SPLIT -- fp32 tensors only: the products as fp16 hi / lo parts on the 16-bit MFMA
 // (attn_prefix_*_split) instead of the exact-fp32 VALU kernels
+// CLIPK_PREFIX_OUT_SPLIT (forward, with CLIPK_PREFIX_SPLIT only) -- o stored in the pre-split form
+// of CLIPK_A_SPLIT, for out_proj's A; the backward takes no such o (its flag set excludes it)
 constexpr int kPrefixFlags = CLIPK_PREFIX_CLS_GROUP0 | CLIPK_PREFIX_SPLIT;
+constexpr int kPrefixFwdFlags = kPrefixFlags | CLIPK_PREFIX_OUT_SPLIT;
 static int prefix_fwd_call(int dtype, int G, int P, int R, int ntiles, const int* tiles, const int* row_first,
                            int heads, const void* qkv, int ldqkv, void* out, int ldo, float* lse, int flags,
                            void* stream) {
   if (!tiles || !row_first || !qkv || !out) return CLIPK_EINVAL;
-  if (flags & ~kPrefixFlags) return CLIPK_EINVAL;
+  if (flags & ~kPrefixFwdFlags) return CLIPK_EINVAL;
   if ((flags & CLIPK_PREFIX_SPLIT) && dtype != CLIPK_F32) return CLIPK_EINVAL;
+  // whole 8-column groups per row of o (ldo % 8, checked for every call below)
+  if ((flags & CLIPK_PREFIX_OUT_SPLIT) && (!(flags & CLIPK_PREFIX_SPLIT) || ldo % 8)) return CLIPK_EINVAL;
   if (!prefix_shape_ok(G, P, R, ntiles, heads, ldqkv) || ldqkv < 3 * heads * 64 || ldo < heads * 64 ||
       ldqkv % 8 || ldo % 8)
     return CLIPK_ESHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int c0 = (flags & CLIPK_PREFIX_CLS_GROUP0) ? 1 : 0;
   if (flags & CLIPK_PREFIX_SPLIT)
-    return prefix_fwd_split(G, P, R, ntiles, tiles, row_first, heads, qkv, ldqkv, out, ldo, lse, st, c0);
+    return prefix_fwd_split(G, P, R, ntiles, tiles, row_first, heads, qkv, ldqkv, out, ldo, lse, st, c0,
+                            (flags & CLIPK_PREFIX_OUT_SPLIT) != 0);
   switch (dtype) {
     case CLIPK_F16: return prefix_fwd<f16>(G, P, R, ntiles, tiles, row_first, heads, qkv, ldqkv, out, ldo, lse, st, c0);
     case CLIPK_BF16: return prefix_fwd<bf16>(G, P, R, ntiles, tiles, row_first, heads, qkv, ldqkv, out, ldo, lse, st, c0);

@@ -57,6 +57,9 @@ struct clipk_encoder {
     const float *A = nullptr, *B = nullptr;
     float *dA = nullptr, *dB = nullptr;
   } lora;
+  // set by a saving text forward: its saved o tensors hold the pre-split form (CLIPK_PREFIX_OUT_SPLIT),
+  // which no backward kernel may read as fp32 values (text_backward_impl checks)
+  mutable int o_saved_split = 0;
 };
 
 namespace clipk {
@@ -67,10 +70,13 @@ static inline size_t esize(int dt) { return (dt == CLIPK_F32 || dt == CLIPK_F32S
 // weights (CLIPK_F32S). Set per call (RAII, per host thread) by the entry points below, so the
 // shared layer-loop code keeps passing the activation dtype.
 static thread_local int t_split = 0;
+// ... and, set by the text forward (o_split_on), its attention stores o pre-split for out_proj
+static thread_local bool t_osplit = false;
 struct SplitScope {
   int prev;
-  explicit SplitScope(const clipk_encoder* e) : prev(t_split) { t_split = e->split; }
-  ~SplitScope() { t_split = prev; }
+  bool prev_o;
+  explicit SplitScope(const clipk_encoder* e) : prev(t_split), prev_o(t_osplit) { t_split = e->split; t_osplit = false; }
+  ~SplitScope() { t_split = prev; t_osplit = prev_o; }
 };
 static inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 
@@ -405,7 +411,9 @@ static int attn_fwd(const clipk_encoder* e, const SeqShape& sh, const void* qkv,
   const int W = e->W;
   if (sh.packed)
     return clipk_attention_prefix_fwd_ex(e->act, sh.G, sh.P, sh.R, sh.ntiles, sh.tiles, sh.row_first, e->heads,
-                                         qkv, 3 * W, o, W, lse, pflags | prefix_split_flag(e, kPrefixSplitFwd), st);
+                                         qkv, 3 * W, o, W, lse,
+                                         pflags | prefix_split_flag(e, kPrefixSplitFwd) |
+                                             (t_osplit ? CLIPK_PREFIX_OUT_SPLIT : 0), st);
   return clipk_attention_fwd(e->act, sh.nseq, sh.L, e->heads, sh.causal, qkv, 3 * W, o, W, lse, st);
 }
 
@@ -530,6 +538,17 @@ static int gemm_ln_split2(int epi, int M, int N, int K, const void* A, const voi
 }
 // the fold-side hand-off of gemm_ln_split2 is on for this call: split mode 2, pre-split hand-offs
 static bool ps_fold(const clipk_encoder* e) { return t_split == 2 && e->split == 2 && presplit_on(); }
+// o handed to out_proj pre-split (the last A operand of the fp32s text step that a K loop split
+// itself): the split prefix forward stores o's fp16 parts (CLIPK_PREFIX_OUT_SPLIT) and the out_proj
+// producer reads them with CLIPK_A_SPLIT -- bitwise the parts it formed. On where the split forward
+// kernels run on packed rows (both directions: the fp32 VALU backward reads o) and the fold's
+// pre-split hand-offs are on in split mode 2; LoRA and every other path keep an fp32 o. Knob
+// CLIPK_PRESPLIT_O=0 (read at every call): fp32 o.
+static bool o_split_on(const clipk_encoder* e, const SeqShape& sh, bool fold) {
+  const char* s = getenv("CLIPK_PRESPLIT_O");
+  return (s ? atoi(s) != 0 : true) && fold && ps_fold(e) && sh.packed && e->lora.rank == 0 &&
+         prefix_split_flag(e, kPrefixSplitFwd) != 0 && prefix_split_bwd(e, sh, e->grad);
+}
 // mean / rstd (kept for the LayerNorm backward) and the folding GEMM's (rstd, -rstd mean) pairs
 static int ln_merge(int rows, int W, const float* lnst, float* m, float* r, float* rnb, hipStream_t st, bool text) {
   ProfScope ps(CLIPK_PROF_NONE, st, 0.0, text ? "text.ln_stats" : "vit.ln_stats", (double)rows * (W / 64) * 8 + 16.0 * rows);
@@ -578,8 +597,10 @@ static int block_post_fold(const clipk_encoder* e, const std::array<const void*,
   const int pg = text ? CLIPK_PROF_GEMM_ALL : CLIPK_PROF_NONE;
   const float* g2 = e->split == 2 ? (const float*)w[6] : nullptr;
   if (xs)
-    TRY(gemm_ln_split2(CLIPK_EPI_BIAS_RES, rows, W, W, o, w[4], (const float*)w[5], X, Xm, lnst, g2, xs, st, pg,
-                       text ? "text.out_fwd" : "vit.out_fwd"));
+    TRY(gemm_ln_split2(CLIPK_EPI_BIAS_RES | (t_osplit ? CLIPK_A_SPLIT : 0), rows, W, W, o, w[4], (const float*)w[5], X,
+                       Xm, lnst, g2, xs, st, pg, text ? "text.out_fwd" : "vit.out_fwd"));
+  else if (t_osplit)
+    return CLIPK_EINVAL;  // a pre-split o has one reader, the producer above
   else
     TRY(gemm_ln(act, CLIPK_EPI_BIAS_RES, rows, W, W, o, w[4], (const float*)w[5], X, Xm, nullptr, lnst, nullptr,
                 nullptr, st, pg, text ? "text.out_fwd" : "vit.out_fwd"));
@@ -849,6 +870,8 @@ static int text_forward_impl(const clipk_encoder* e, const SeqShape& sh, const f
   const bool eotl = text_eot_last(sh);
   const int nl = e->layers, nout = sh.nout;
   const bool fold = ln_fold_on(e, io);
+  t_osplit = io.text && o_split_on(e, sh, fold);  // (split_scope restores it)
+  if (save) e->o_saved_split = t_osplit;
   bool have_stats = false;  // LN fold: t.lnst holds the statistics partials of cur
   bool xs_ready = false;    // t.xn holds split(cur * the next ln_1 weight) (block_post_fold)
   for (int l = 0; l < nl; ++l) {
@@ -946,6 +969,8 @@ static int text_backward_impl(const clipk_encoder* e, const SeqShape& sh, const 
   if (saved_bytes < t.saved_bytes || ws_bytes < b.bytes) return CLIPK_EWORKSPACE;
   const int W = e->W, rows = sh.rows, nout = sh.nout, gd = e->grad, act = e->act;
   const int pg = io.text ? CLIPK_PROF_GEMM_ALL : CLIPK_PROF_NONE;
+  // the forward saved o pre-split: only the split attention backward (which reads no o) may run
+  if (e->o_saved_split && !prefix_split_bwd(e, sh, gd)) return CLIPK_EINVAL;
   float* dX = dx0;
   // d lnf = dtxt . P^T   (txt = lnf @ P, P = projection [W,E])
   if (e->split) {

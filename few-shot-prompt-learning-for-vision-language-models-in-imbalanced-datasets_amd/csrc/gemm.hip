@@ -124,6 +124,37 @@ bool gemm_t96() {
   }
   return v != 0;
 }
+// knob CLIPK_GEMM_T256: 0 = never 256-row split tiles (the 192-row launches only), 1 (default) =
+// by split_tile_rows' rule, 2 = always where a 256-row instantiation exists
+static int gemm_t256() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("CLIPK_GEMM_T256");
+    v = e ? atoi(e) : 1;
+    if (v < 0 || v > 2) v = 1;
+  }
+  return v;
+}
+// Cost of one 256-row tile over one 192-row tile of the same class, measured: each class alone at
+// the headline shape (M = 47,160, K = 512, A rotated through > 600 MB), both heights, three
+// interleaved repeats of 7 x 20 launches (tools/t256_gemm_bench.py; profiles/t256/isolated.txt),
+// per-tile cost = us per launch / tiles on the busiest CU.
+//   c_fc fold (N = 2048, 8 vs 6 tiles per CU): 281-284 -> 262-269 us per launch, ratio 1.24-1.28
+//   qkv fold  (N = 1536, 6 vs 5 tiles per CU): 162-166 -> 154-156 us per launch, ratio 1.12-1.16
+// (256 rows pay while the ratio stays under the tile-count ratio: 8/6 and 6/5 there)
+static const double kT256Cost[3] = {0.0, 1.26, 1.14};
+static int busiest(int M, int N, int bm, int cus) {
+  const long tiles = (long)((M + bm - 1) / bm) * (N / 256);
+  const int grid = pp_grid((int)(tiles < 0x7fffffff ? tiles : 0x7fffffff), cus);
+  return (int)((tiles + grid - 1) / grid);
+}
+int split_tile_rows(int cls, int M, int N) {
+  const int mode = gemm_t256();
+  if (cls <= T256_NONE || cls > T256_QKV || mode == 0) return 192;
+  if (mode == 2) return 256;
+  const int cus = num_cus();
+  return busiest(M, N, 256, cus) * kT256Cost[cls] < (double)busiest(M, N, 192, cus) ? 256 : 192;
+}
 static int g_num_cus = 0;
 int num_cus() {
   if (!g_num_cus) {
@@ -603,6 +634,24 @@ static int dispatch_ln_merge(int epi, const GemmArgs& g, hipStream_t st) {
 
 extern "C" int clipk_gemm_ln_merge_fused(int in_dtype, int M, int N, int K) {
   return ln_merge_fused_ok(in_dtype, M, N, K) ? 1 : 0;
+}
+
+// the 256-row class of a split launch as the C-ABI names it (epi with its operand flags)
+static int t256_class_of(int in_dtype, int epi, int lnm) {
+  const int spf = split_flags(epi);
+  int e = epi & ~(CLIPK_QGELU_DERIV | CLIPK_A_SPLIT | CLIPK_OUT_SPLIT | CLIPK_OUT2_SPLIT_GAMMA);
+  if (epi & CLIPK_QGELU_DERIV) e = e == CLIPK_EPI_BIAS_QGELU ? EPI_QGELU_D : e == CLIPK_EPI_DQGELU ? EPI_DMUL : -1;
+  return t256_class(in_dtype == CLIPK_F32S16, e, lnm, spf);
+}
+extern "C" int clipk_gemm_split_tile_rows(int in_dtype, int epi, int lnm, int M, int N) {
+  if (in_dtype != CLIPK_F32S && in_dtype != CLIPK_F32S16) return CLIPK_EDTYPE;
+  if (M <= 0 || N <= 0 || N % GEMM_NMIN != 0) return CLIPK_ESHAPE;
+  const int cfg = pick_cfg(M, N, 2);
+  if (cfg != 1 && cfg != 6) return 0;
+  return split_tile_rows(t256_class_of(in_dtype, epi, lnm), M, N);
+}
+extern "C" double clipk_gemm_t256_cost(int in_dtype, int epi, int lnm) {
+  return kT256Cost[t256_class_of(in_dtype, epi, lnm)];
 }
 
 // LayerNorm fold with the statistics merge (include/clipk.h): what clipk_ln_stats_merge +

@@ -1146,10 +1146,31 @@ static bool try_pp(const GemmArgs& g, int nwg, hipStream_t st) {
   return false;
 }
 
+// ---- 256-row ping-pong tiles for the pre-split f32h GEMMs (split mode 2). With A pre-split the K
+// loop holds no split temporaries, so these classes fit 256 VGPRs with no scratch (the register
+// table is in profiles/t256/summary.txt); a 256x256 K step stages 48 KiB for 65,536 MACs per k
+// against 40 KiB for 49,152 on 192 rows. The classes built at 256 rows:
+enum { T256_NONE = 0, T256_FC = 1, T256_QKV = 2 };
+// (w16: f32h; epi the internal epilogue id; lnm / spf the kernel's LNM / SPF)
+constexpr int t256_class(bool w16, int epi, int lnm, int spf) {
+  if (!w16 || lnm != 4) return T256_NONE;
+  if (spf == 3 && epi_qgelu(epi)) return T256_FC;           // the c_fc fold (A and out pre-split)
+  if (spf == 1 && epi == CLIPK_EPI_BIAS) return T256_QKV;   // the qkv fold
+  // dgelu (EPI_DMUL, SPF 3) stays on 192 rows: its 256-row form is 256 VGPRs + 9 spilled (237
+  // without its fp32 aux operand: the one-row-group prefetch ring, 16 VGPRs, is what does not fit;
+  // try_pp keeps refusing BM == 256 with an fp32 residual / aux operand)
+  return T256_NONE;
+}
+// Tile height (192 or 256) of a split ping-pong launch of class cls at (M, N): the smaller of
+// (tiles on the busiest CU) x (cost of one tile); knob CLIPK_GEMM_T256 (0 never 256 rows, 1 by
+// this rule, 2 always where built). Defined in gemm.hip.
+int split_tile_rows(int cls, int M, int N);
+
 // PREC fp32s (CLIPK_F32S) launches: fp32 out / residual / aux. Large M (where the 16-bit policy
-// picks the 192- or 256-row tiles): the ping-pong loop on 192x256 tiles (256-row ones spill at
-// 256 VGPRs with the split's temporaries); otherwise 128x128 tiles (a 4-slot ring when the grid
-// is at most one tile per CU).
+// picks the 192- or 256-row tiles): the ping-pong loop on 192x256 tiles, or on 256x256 tiles for
+// the pre-split classes above where split_tile_rows says so (the f32s kernels, the residual
+// producers at 214-238 VGPRs and every GEMM that splits A in its loop keep 192 rows); otherwise
+// 128x128 tiles (a 4-slot ring when the grid is at most one tile per CU).
 // (Until the split8 hazard above was found, CLIPK_F32S16 ran the 2-MFMA kernel on the ping-pong
 // tiles only: on the 2- / 4-slot loop it measured not bit-identical. With the compiler-visible
 // split there it is bitwise the 3-MFMA kernel on every tile path, profiles/r05w16/hazard.txt.)
@@ -1171,6 +1192,14 @@ static int launch_gemm_split(const GemmArgs& g, hipStream_t st) {
     return CLIPK_OK;
   }
   if (cfg == 1 || cfg == 6) {
+    constexpr int T256 = t256_class(__is_same(TS, f32h), EPI, LNM, SPF);
+    if constexpr (T256 != T256_NONE) {
+      if (split_tile_rows(T256, g.M, g.N) == 256 &&
+          try_pp<TS, float, float, EPI, 256, LNM, SPF>(g, ((g.M + 255) / 256) * (g.N / 256), st)) {
+        CLIPK_CHECK_LAUNCH();
+        return CLIPK_OK;
+      }
+    }
     if (try_pp<TS, float, float, EPI, 192, LNM, SPF>(g, ((g.M + 191) / 192) * (g.N / 256), st)) {
       CLIPK_CHECK_LAUNCH();
       return CLIPK_OK;

@@ -211,6 +211,17 @@ int clipk_gemm_ln_merge(int in_dtype, int epi, int M, int N, int K, const void* 
                         const float* colsum, float* mean, float* rstd, float* rnb, void* stream);
 /* 1 when clipk_gemm_ln_merge runs the shape as one launch, 0 when as the two calls. */
 int clipk_gemm_ln_merge_fused(int in_dtype, int M, int N, int K);
+/* PREC fp32s tile policy query (in_dtype CLIPK_F32S / CLIPK_F32S16; epi with its operand flags as
+ * the launching call takes it; lnm 0 for clipk_gemm, 1 / 2 for clipk_gemm_ln's producer / fold, 4
+ * for clipk_gemm_ln_gamma): the height of the ping-pong tile such a launch takes at (M, N) -- 192,
+ * or 256 for the pre-split classes built at 256 rows (split mode 2: the c_fc and qkv folds with
+ * CLIPK_A_SPLIT) where (tiles on the busiest CU) x (cost of one tile) is smaller; 0 where the
+ * shape does not run the ping-pong tiles. Knob CLIPK_GEMM_T256 (read once per process): 0 never
+ * 256 rows, 1 (default) by that rule, 2 always where built. Outputs are bitwise the same at
+ * either height. clipk_gemm_t256_cost: the rule's cost of a 256-row tile over a 192-row one for
+ * the launch's class, 0 where none is built. */
+int clipk_gemm_split_tile_rows(int in_dtype, int epi, int lnm, int M, int N);
+double clipk_gemm_t256_cost(int in_dtype, int epi, int lnm);
 /* Benchmark knob: force the 16-bit GEMM tile configuration (0: 128x128, 1: 256x256
  * (persistent above 2 x CUs tiles), 2: 256x128, 3: 256x256 non-persistent, 6: 192x256;
  * -1 = automatic by shape; other values: CLIPK_EINVAL). Not needed for normal use. */
@@ -323,8 +334,13 @@ int clipk_attention_prefix_bwd(int dtype, int grad_dtype, int G, int P, int R, i
  * CLIPK_F32S; softmax, lse and delta = sum_j P.dP stay fp32. Valid only with dtype CLIPK_F32 (the
  * backward: grad_dtype CLIPK_F32 or CLIPK_F32S), otherwise CLIPK_EINVAL; combines with
  * CLIPK_PREFIX_CLS_GROUP0. The backward accepts ofwd and does not read it. A part beyond fp16's
- * range gives inf / NaN outputs. Without the flag the fp32 calls run the exact-fp32 kernels. */
-enum { CLIPK_PREFIX_CLS_GROUP0 = 1, CLIPK_PREFIX_SPLIT = 2 };
+ * range gives inf / NaN outputs. Without the flag the fp32 calls run the exact-fp32 kernels.
+ * CLIPK_PREFIX_OUT_SPLIT (forward only) -- out is stored in the pre-split form of CLIPK_A_SPLIT
+ * (per 8 consecutive columns 16 B of hi parts, then 16 B of lo parts, of the fp32 o the call
+ * stores without the flag: bitwise the parts a split GEMM forms from it), for out_proj's A. Valid
+ * only together with CLIPK_PREFIX_SPLIT and ldo % 8 == 0, otherwise CLIPK_EINVAL; the backward
+ * rejects the flag (CLIPK_EINVAL): no kernel reads such an o as fp32 values. lse is unchanged. */
+enum { CLIPK_PREFIX_CLS_GROUP0 = 1, CLIPK_PREFIX_SPLIT = 2, CLIPK_PREFIX_OUT_SPLIT = 4 };
 int clipk_attention_prefix_fwd_ex(int dtype, int G, int P, int R, int ntiles, const int* tiles,
                                   const int* row_first, int heads, const void* qkv, int ldqkv, void* out,
                                   int ldo, float* lse, int flags, void* stream);
