@@ -38,6 +38,8 @@ F32, F16, BF16, F32S = 0, 1, 2, 3  # F32S: fp32 activations x split-packed weigh
 PREFIX_CLS_GROUP0 = 1  # clipk_attention_prefix_*_ex flag
 PREFIX_SPLIT = 2  # ... fp32 tensors on the 16-bit MFMA as fp16 hi / lo parts (PREC fp32s)
 PREFIX_OUT_SPLIT = 4  # ... forward, with PREFIX_SPLIT: o stored pre-split (the form of A_SPLIT) for out_proj
+ATTN_SPLIT = 1  # clipk_attention_fwd_ex flag: fp32 tensors on the 16-bit MFMA as fp16 hi / lo parts (L > 16)
+ATTN_OUT_SPLIT = 2  # ... with ATTN_SPLIT: o stored pre-split (the form of A_SPLIT) for out_proj
 F32S16 = 4  # F32S for fp16-valued weights: B is the compact fp16 SPLIT_SCALE * W (clipk_split_hi16)
 SPLIT_SCALE = 64.0  # CLIPK_SPLIT_SCALE: clipk_split_pack stores SPLIT_SCALE * W
 EPI_BIAS, EPI_BIAS_RES, EPI_BIAS_QGELU, EPI_DQGELU, EPI_NONE = 0, 1, 2, 3, 4
@@ -85,6 +87,7 @@ SIGNATURES = {
     "clipk_layernorm_bwd_x": (_I, [_I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P]),
     "clipk_layernorm_bwd_x2": (_I, [_I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _I, _P]),
     "clipk_attention_fwd": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P]),
+    "clipk_attention_fwd_ex": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     "clipk_attention_bwd": (_I, [_I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P]),
     "clipk_im2col": (_I, [_I, _I, _I, _I, _I, _P, _P, _P]),
     "clipk_vit_embed_ln": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),

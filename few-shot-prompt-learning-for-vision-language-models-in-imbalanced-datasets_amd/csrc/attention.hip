@@ -97,7 +97,8 @@ __global__ __launch_bounds__(256) void attn_fwd_short(int nseq, int L, int H, in
 }
 
 // ------------------------------------------------------------------ forward, any L, fp32
-// (PREC fp32 / fp32s: the ViT's L = 50..577, plain text 64 < L <= 77). Block = 64 query rows of
+// (PREC fp32, and calls without CLIPK_ATTN_SPLIT: the ViT's L = 50..577, plain text 64 < L <= 77;
+// PREC fp32s runs attn_fwd_split below). Block = 64 query rows of
 // one (sequence, head), 4 waves of 16 rows; lane = 4 r + s holds row r's 16-column slice s of q
 // and o (the interleaved map of attn_common.h); K / V in 64-key LDS chunks, a score is 16 FMAs
 // + a quad sum, exact online softmax.
@@ -522,6 +523,182 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_t(int nseq, int L, int H, i
   }
 }
 
+// ------------------------------------------------------------------ forward, L > 16, fp32 on the 16-bit MFMA
+// (CLIPK_ATTN_SPLIT, PREC fp32s: the ViT's L = 50..577, plain text 16 < L <= 77.) attn_fwd_mfma_t's
+// structure -- 4 waves = 64 query rows of one (sequence, head), 64-key chunks through LDS, S^T = K Q^T,
+// O accumulated transposed, one log2-domain softmax update per 32 keys, the rescale skipped when no
+// running max moved, the next chunk in flight in registers -- on fp32 tensors: every operand element x
+// is taken as hi = fp16(x), lo = fp16(x - hi) and every product as lo.hi + hi.lo + hi.hi with fp32
+// accumulation (the three-term rule of attn_prefix_fwd_split and the CLIPK_F32S GEMMs).
+//  * q / 8 (exact) is split once into registers;
+//  * K and V are split as the chunk is written to LDS: four fp16 tiles (K hi, K lo, V hi, V lo) of
+//    64 x TRS, 36 KiB. The lo parts are v_fma_mix (split_lo4); their consumers are LDS stores;
+//  * P is split in registers after the exact scale by kPScale (split_pack4: compiler-visible code, so
+//    hipcc places the MFMA wait states), undone by the final 1 / l factor;
+//  * the two small terms of a score accumulate apart from the hi.hi term (two independent MFMA
+//    chains per 16 keys) and are added once;
+//  * scaling, mask, max, exp2, the row sum, lse and 1 / l stay fp32. No range scaling: a part beyond
+//    fp16's range gives an inf / NaN output (the encoder's finite check reports it).
+// A 32-key group past the last key -- or, causal, past the wave's last query -- is skipped.
+// OS (CLIPK_ATTN_OUT_SPLIT): o stored in the pre-split CLIPK_A_SPLIT form, the parts of the fp32 o.
+template <bool OS>
+__global__ __launch_bounds__(256) void attn_fwd_split(int nseq, int L, int H, int causal,
+                                                      const float* __restrict__ qkv, int ldq,
+                                                      float* __restrict__ out, int ldo,
+                                                      float* __restrict__ lse) {
+  __shared__ CLIPK_LDS_ALIGN short sKh[64 * TRS];
+  __shared__ CLIPK_LDS_ALIGN short sKl[64 * TRS];
+  __shared__ CLIPK_LDS_ALIGN short sVh[64 * TRS];
+  __shared__ CLIPK_LDS_ALIGN short sVl[64 * TRS];
+  constexpr float kLog2e = 1.4426950408889634f;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int r16 = lane & 15, g4 = lane >> 4;
+  const int h = blockIdx.y, s = blockIdx.z;
+  const int W = H * 64;
+  const size_t row0 = (size_t)s * L;
+  const int q0 = blockIdx.x * 64 + w * 16;
+  const int qr = q0 + r16;
+  const bool qok = qr < L;
+  s16x8 qh[2], ql[2];  // row qr's columns 8 g4 + 32 kk .. + 7 of q / 8 (zero past L)
+  {
+    const float* qp = qkv + (row0 + (qok ? qr : 0)) * ldq + h * 64 + 8 * g4;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      f32x4 x[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+        x[c] = qok ? *reinterpret_cast<const f32x4*>(qp + 32 * kk + 4 * c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      f16x8 hh, ll;
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          f16 ph, pl;
+          split_parts(x[c][e] * kScale, ph, pl);
+          hh[4 * c + e] = ph;
+          ll[4 * c + e] = pl;
+        }
+      qh[kk] = __builtin_bit_cast(s16x8, hh);
+      ql[kk] = __builtin_bit_cast(s16x8, ll);
+    }
+  }
+
+  f32x4 o[4];  // o[t][r] = kPScale * O[query r16][dim 16 t + 4 g4 + r]
+#pragma unroll
+  for (int t = 0; t < 4; ++t) o[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;  // running max (log2 domain, replicated over g4), lane-partial sum
+  const int qmax = min(L, (int)(blockIdx.x + 1) * 64) - 1;
+  const int kend = causal ? qmax + 1 : L;
+  // K / V chunk staging: thread tid moves 8 columns (32 B) of rows (tid >> 3) and 32 + (tid >> 3)
+  f32x4 rk[2][2], rv[2][2];
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int kr = k0 + it * 32 + (tid >> 3), ch = tid & 7;
+      const bool ok = kr < L;
+      const float* base = qkv + (row0 + (ok ? kr : 0)) * ldq + h * 64 + ch * 8;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        rk[it][c] = ok ? *reinterpret_cast<const f32x4*>(base + W + 4 * c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        rv[it][c] = ok ? *reinterpret_cast<const f32x4*>(base + 2 * W + 4 * c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  };
+  // 8 fp32 values -> 16 B of hi parts and 16 B of lo parts at the same offset of two tiles
+  auto st_split = [&](const f32x4& a, const f32x4& b, short* thi, short* tlo) {
+    const unsigned h01 = __builtin_bit_cast(unsigned, (f16x2){(f16)a[0], (f16)a[1]});
+    const unsigned h23 = __builtin_bit_cast(unsigned, (f16x2){(f16)a[2], (f16)a[3]});
+    const unsigned h45 = __builtin_bit_cast(unsigned, (f16x2){(f16)b[0], (f16)b[1]});
+    const unsigned h67 = __builtin_bit_cast(unsigned, (f16x2){(f16)b[2], (f16)b[3]});
+    unsigned l01, l23, l45, l67;
+    split_lo4(a[0], a[1], a[2], a[3], h01, h23, l01, l23);
+    split_lo4(b[0], b[1], b[2], b[3], h45, h67, l45, l67);
+    *reinterpret_cast<u32x4*>(thi) = (u32x4){h01, h23, h45, h67};
+    *reinterpret_cast<u32x4*>(tlo) = (u32x4){l01, l23, l45, l67};
+  };
+  fetch(0);
+  for (int k0 = 0; k0 < kend; k0 += 64) {
+    __syncthreads();  // the previous chunk's readers are done
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int off = (it * 32 + (tid >> 3)) * TRS + (tid & 7) * 8;
+      st_split(rk[it][0], rk[it][1], sKh + off, sKl + off);
+      st_split(rv[it][0], rv[it][1], sVh + off, sVl + off);
+    }
+    __syncthreads();
+    if (k0 + 64 < kend) fetch(k0 + 64);  // in flight while this chunk is consumed
+    const int npair = min(2, (kend - k0 + 31) / 32);
+    for (int pc = 0; pc < npair; ++pc) {
+      const int kb = pc * 32;  // first key of the 32 within the chunk
+      const int kabs = k0 + kb;
+      if (causal && kabs > q0 + 15) break;  // wave-uniform: every key is past the wave's last query
+      float sv[8];
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub) {
+        f32x4 sb = {0.f, 0.f, 0.f, 0.f}, ss = {0.f, 0.f, 0.f, 0.f};  // hi.hi, and the two small terms
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+          const int off = (kb + sub * 16 + r16) * TRS + 8 * g4 + 32 * kk;
+          const s16x8 kh = *reinterpret_cast<const s16x8*>(sKh + off);
+          const s16x8 kl = *reinterpret_cast<const s16x8*>(sKl + off);
+          ss = mfma32_t<f16>(kl, qh[kk], ss);
+          ss = mfma32_t<f16>(kh, ql[kk], ss);
+          sb = mfma32_t<f16>(kh, qh[kk], sb);  // [r] = S[query r16][key kb + 16 sub + 4 g4 + r]
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sv[4 * sub + r] = (sb[r] + ss[r]) * kLog2e;
+      }
+      if (kabs + 32 > L || (causal && kabs + 31 > q0)) {  // wave-uniform: edge group only
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int key = kabs + (j < 4 ? 4 * g4 + j : 16 + 4 * g4 + j - 4);
+          if (key >= L || (causal && key > qr)) sv[j] = -INFINITY;
+        }
+      }
+      float mx = sv[0];
+#pragma unroll
+      for (int j = 1; j < 8; ++j) mx = fmaxf(mx, sv[j]);
+      mx = xmax4(mx);
+      const float mn = fmaxf(m, mx);
+      const float msafe = mn == -INFINITY ? 0.f : mn;
+      float p[8], ps = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        p[j] = __builtin_amdgcn_exp2f(sv[j] - msafe);
+        ps += p[j];
+      }
+      if (__builtin_amdgcn_ballot_w64(mn > m) != 0) {  // some query's max moved: rescale
+        const float corr = __builtin_amdgcn_exp2f(m - msafe);  // m = -inf -> 0 (O, l are 0)
+        l *= corr;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) o[t] *= corr;
+      }
+      l += ps;
+      m = mn;
+      s16x4 ph[2], pl[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+        split_pack4(p[4 * c] * kPScale, p[4 * c + 1] * kPScale, p[4 * c + 2] * kPScale, p[4 * c + 3] * kPScale,
+                    ph[c], pl[c]);
+      const s16x8 pbh = __builtin_shufflevector(ph[0], ph[1], 0, 1, 2, 3, 4, 5, 6, 7);
+      const s16x8 pbl = __builtin_shufflevector(pl[0], pl[1], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const s16x8 vh = __builtin_shufflevector(tr_read(sVh, kb + 4 * g4, 16 * t, lane),
+                                                 tr_read(sVh, kb + 16 + 4 * g4, 16 * t, lane), 0, 1, 2, 3, 4, 5, 6, 7);
+        const s16x8 vl = __builtin_shufflevector(tr_read(sVl, kb + 4 * g4, 16 * t, lane),
+                                                 tr_read(sVl, kb + 16 + 4 * g4, 16 * t, lane), 0, 1, 2, 3, 4, 5, 6, 7);
+        o[t] = mfma32_t<f16>(vl, pbh, o[t]);
+        o[t] = mfma32_t<f16>(vh, pbl, o[t]);
+        o[t] = mfma32_t<f16>(vh, pbh, o[t]);
+      }
+    }
+  }
+  const float lt = xsum4(l);
+  store_acc64<OS>(out + (row0 + (qok ? qr : 0)) * ldo + h * 64, o, kPInv / lt, qok, g4);  // every lane (OS: swaps)
+  if (lse && g4 == 0 && qok) lse[(row0 + qr) * H + h] = (m + __log2f(lt)) * 0.6931471805599453f;
+}
+
 // ------------------------------------------------------------------ backward, any L (vision)
 // The ViT's input-grad backward (deep visual prompts, IVLP / MaPLe / PromptSRC: model.py:
 // 191-331, 401-431): L = 50..600 rows per sequence, non-causal (causal supported). Two passes
@@ -932,21 +1109,51 @@ static int launch_bwd(int nseq, int L, int H, int causal, const void* qkv, int l
 
 using namespace clipk;
 
-extern "C" int clipk_attention_fwd(int dtype, int nseq, int L, int heads, int causal,
-                                   const void* qkv, int ldqkv, void* out, int ldo, float* lse,
-                                   void* stream) {
+// flags (clipk_attention_fwd_ex; every refusal below comes before any launch):
+// CLIPK_ATTN_SPLIT -- fp32 tensors only: L > 16 runs attn_fwd_split (the products as fp16 hi / lo
+// parts on the 16-bit MFMA) instead of the exact-fp32 kernels; L <= 16 runs the exact short kernel
+// CLIPK_ATTN_OUT_SPLIT (with CLIPK_ATTN_SPLIT, L > 16, ldo % 8 == 0 only) -- o stored in the
+// pre-split form of CLIPK_A_SPLIT, for out_proj's A; the backward takes no such o
+static int attention_fwd_call(int dtype, int nseq, int L, int heads, int causal, const void* qkv, int ldqkv,
+                              void* out, int ldo, float* lse, int flags, void* stream) {
   if (!qkv || !out) return CLIPK_EINVAL;
+  if (flags & ~(CLIPK_ATTN_SPLIT | CLIPK_ATTN_OUT_SPLIT)) return CLIPK_EINVAL;
+  if (flags && dtype != CLIPK_F32) return CLIPK_EINVAL;
+  if ((flags & CLIPK_ATTN_OUT_SPLIT) && (!(flags & CLIPK_ATTN_SPLIT) || ldo % 8 || L <= 16)) return CLIPK_EINVAL;
   if (nseq < 0 || L <= 0 || heads <= 0 || ldqkv < 3 * heads * 64 || ldo < heads * 64 || ldqkv % 8 ||
       ldo % 8)
     return CLIPK_ESHAPE;
   if (nseq == 0) return CLIPK_OK;
   hipStream_t st = (hipStream_t)stream;
+  if ((flags & CLIPK_ATTN_SPLIT) && L > 16) {
+    dim3 grid((L + 63) / 64, heads, nseq);
+    if (flags & CLIPK_ATTN_OUT_SPLIT)
+      hipLaunchKernelGGL((attn_fwd_split<true>), grid, dim3(256), 0, st, nseq, L, heads, causal, (const float*)qkv,
+                         ldqkv, (float*)out, ldo, lse);
+    else
+      hipLaunchKernelGGL((attn_fwd_split<false>), grid, dim3(256), 0, st, nseq, L, heads, causal, (const float*)qkv,
+                         ldqkv, (float*)out, ldo, lse);
+    CLIPK_CHECK_LAUNCH();
+    return CLIPK_OK;
+  }
   switch (dtype) {
     case CLIPK_F16: return launch_fwd<f16>(nseq, L, heads, causal, qkv, ldqkv, out, ldo, lse, st);
     case CLIPK_BF16: return launch_fwd<bf16>(nseq, L, heads, causal, qkv, ldqkv, out, ldo, lse, st);
     case CLIPK_F32: return launch_fwd<float>(nseq, L, heads, causal, qkv, ldqkv, out, ldo, lse, st);
     default: return CLIPK_EDTYPE;
   }
+}
+
+extern "C" int clipk_attention_fwd(int dtype, int nseq, int L, int heads, int causal,
+                                   const void* qkv, int ldqkv, void* out, int ldo, float* lse,
+                                   void* stream) {
+  return attention_fwd_call(dtype, nseq, L, heads, causal, qkv, ldqkv, out, ldo, lse, 0, stream);
+}
+
+extern "C" int clipk_attention_fwd_ex(int dtype, int nseq, int L, int heads, int causal,
+                                      const void* qkv, int ldqkv, void* out, int ldo, float* lse,
+                                      int flags, void* stream) {
+  return attention_fwd_call(dtype, nseq, L, heads, causal, qkv, ldqkv, out, ldo, lse, flags, stream);
 }
 
 extern "C" int clipk_attention_bwd(int dtype, int grad_dtype, int nseq, int L, int heads,

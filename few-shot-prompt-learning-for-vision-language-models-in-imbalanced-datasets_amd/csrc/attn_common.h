@@ -268,4 +268,53 @@ __device__ __forceinline__ void store_tile64(T* rowp, const f32x4 (&o)[4], float
   }
 }
 
+// ---- fp32 values as fp16 hi / lo parts (PREC fp32s attention: attention_prefix.hip's split kernels,
+// attention.hip's attn_fwd_split). The probabilities are split after an exact scale by kPScale (see
+// attention_prefix.hip); the accumulator or the 1 / l factor undoes it.
+constexpr float kPScale = 4096.0f, kPInv = 1.0f / 4096.0f;
+
+// the parts of 4 computed values (split_parts: of the rounded fp32 value)
+__device__ __forceinline__ void split_pack4(float a, float b, float c, float d, s16x4& hi, s16x4& lo) {
+  float x[4] = {a, b, c, d};
+  typedef f16 h4 __attribute__((ext_vector_type(4)));
+  h4 h, l;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    asm volatile("" : "+v"(x[e]));
+    h[e] = (f16)x[e];
+    l[e] = (f16)(x[e] - (float)h[e]);
+  }
+  hi = __builtin_bit_cast(s16x4, h);
+  lo = __builtin_bit_cast(s16x4, l);
+}
+// Store a 16-row x 64-column accumulator tile (lane (r16, g4): row r16, columns 16 t + 4 g4 .. + 3
+// in a[t]) as fp32, or (OS) in the pre-split CLIPK_A_SPLIT form: the lanes g4 = 2 j, 2 j + 1 hold
+// the halves of an 8-column group and trade parts over v_permlane16_swap -- the even lane row
+// gets its partner's hi parts, the odd one its partner's lo parts -- so each lane stores one whole
+// 16-B half (even: the group's hi parts, odd: its lo parts). Every lane executes it.
+// store_acc16: one 16-column chunk t (v the lane's 4 values of it); rowp the row's column 0.
+template <bool OS>
+__device__ __forceinline__ void store_acc16(float* rowp, const f32x4 v, int t, bool ok, int g4) {
+  if constexpr (!OS) {
+    if (ok) *reinterpret_cast<f32x4*>(rowp + 16 * t + 4 * g4) = v;
+  } else {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    s16x4 h, l;
+    split_pack4(v[0], v[1], v[2], v[3], h, l);
+    const u32x2 hu = __builtin_bit_cast(u32x2, h), lu = __builtin_bit_cast(u32x2, l);
+    // swap(h, l): first = {h.row0, l.row0, h.row2, l.row2} (columns 0-3 of the lane's half),
+    // second = {h.row1, l.row1, h.row3, l.row3} (columns 4-7)
+    const auto s0 = __builtin_amdgcn_permlane16_swap(hu[0], lu[0], false, false);
+    const auto s1 = __builtin_amdgcn_permlane16_swap(hu[1], lu[1], false, false);
+    if (ok)
+      reinterpret_cast<u32x4*>(rowp + 16 * t + 8 * (g4 >> 1))[g4 & 1] =
+          (u32x4){(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
+  }
+}
+template <bool OS>
+__device__ __forceinline__ void store_acc64(float* rowp, const f32x4 (&a)[4], float scale, bool ok, int g4) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) store_acc16<OS>(rowp, a[t] * scale, t, ok, g4);
+}
+
 }  // namespace clipk

@@ -405,6 +405,14 @@ static bool prefix_split_bwd(const clipk_encoder* e, const SeqShape& sh, int gd)
   return sh.packed && gd == CLIPK_F32 && prefix_split_flag(e, kPrefixSplitBwd) != 0;
 }
 
+// ... and on unpacked rows (the ViT, plain text with 16 < L): the forward as attn_fwd_split
+// (CLIPK_ATTN_SPLIT) instead of the fp32 VALU attn_fwd_f32. Knob CLIPK_VIT_SPLIT_ATTN (default on;
+// read at every call): 0 = the exact-fp32 kernel, an fp32 o and out_proj splitting its own A.
+static int attn_split_flag(const clipk_encoder* e) {
+  const char* s = getenv("CLIPK_VIT_SPLIT_ATTN");
+  return (s ? atoi(s) != 0 : true) && e->split != 0 && e->act == CLIPK_F32 ? CLIPK_ATTN_SPLIT : 0;
+}
+
 // pflags: clipk_attention_prefix_*_ex flags (CLIPK_PREFIX_CLS_GROUP0: layer 0 under forward sharing)
 static int attn_fwd(const clipk_encoder* e, const SeqShape& sh, const void* qkv, void* o, float* lse,
                     hipStream_t st, int pflags = 0) {
@@ -414,7 +422,9 @@ static int attn_fwd(const clipk_encoder* e, const SeqShape& sh, const void* qkv,
                                          qkv, 3 * W, o, W, lse,
                                          pflags | prefix_split_flag(e, kPrefixSplitFwd) |
                                              (t_osplit ? CLIPK_PREFIX_OUT_SPLIT : 0), st);
-  return clipk_attention_fwd(e->act, sh.nseq, sh.L, e->heads, sh.causal, qkv, 3 * W, o, W, lse, st);
+  // (t_osplit here: vit_o_split_on, whose conditions the call checks again)
+  return clipk_attention_fwd_ex(e->act, sh.nseq, sh.L, e->heads, sh.causal, qkv, 3 * W, o, W, lse,
+                                attn_split_flag(e) | (t_osplit ? CLIPK_ATTN_OUT_SPLIT : 0), st);
 }
 
 // dqkv_split (shared-prefix packed rows, fp32 gradients): dq|dk|dv stored in the pre-split form the
@@ -548,6 +558,15 @@ static bool o_split_on(const clipk_encoder* e, const SeqShape& sh, bool fold) {
   const char* s = getenv("CLIPK_PRESPLIT_O");
   return (s ? atoi(s) != 0 : true) && fold && ps_fold(e) && sh.packed && e->lora.rank == 0 &&
          prefix_split_flag(e, kPrefixSplitFwd) != 0 && prefix_split_bwd(e, sh, e->grad);
+}
+// The same hand-off on unpacked rows (the frozen ViT's forward-only clipk_vit_forward): attn_fwd_split
+// stores o's parts (CLIPK_ATTN_OUT_SPLIT). Only where nothing reads o as fp32 afterwards: a forward
+// that saves for a backward (the prompted ViT, plain text training) and LoRA keep an fp32 o, so
+// clipk_attention_bwd is never handed a pre-split one.
+static bool vit_o_split_on(const clipk_encoder* e, const SeqShape& sh, bool fold, bool save) {
+  const char* s = getenv("CLIPK_PRESPLIT_O");
+  return (s ? atoi(s) != 0 : true) && !save && fold && ps_fold(e) && !sh.packed && sh.L > 16 && e->lora.rank == 0 &&
+         attn_split_flag(e) != 0;
 }
 // mean / rstd (kept for the LayerNorm backward) and the folding GEMM's (rstd, -rstd mean) pairs
 static int ln_merge(int rows, int W, const float* lnst, float* m, float* r, float* rnb, hipStream_t st, bool text) {
@@ -870,7 +889,7 @@ static int text_forward_impl(const clipk_encoder* e, const SeqShape& sh, const f
   const bool eotl = text_eot_last(sh);
   const int nl = e->layers, nout = sh.nout;
   const bool fold = ln_fold_on(e, io);
-  t_osplit = io.text && o_split_on(e, sh, fold);  // (split_scope restores it)
+  t_osplit = io.text ? o_split_on(e, sh, fold) : vit_o_split_on(e, sh, fold, save);  // (split_scope restores it)
   if (save) e->o_saved_split = t_osplit;
   bool have_stats = false;  // LN fold: t.lnst holds the statistics partials of cur
   bool xs_ready = false;    // t.xn holds split(cur * the next ln_1 weight) (block_post_fold)

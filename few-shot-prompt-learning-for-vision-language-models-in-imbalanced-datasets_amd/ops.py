@@ -270,13 +270,15 @@ def layernorm_bwd_lp_(dy, x, w, mean, rstd, dres_lp, dx=None):
     return dres_lp
 
 
-def attention(qkv, nseq, L, heads, causal, lse=False):
+def attention(qkv, nseq, L, heads, causal, lse=False, flags=0):
+    """flags: N.ATTN_SPLIT (fp32, the products on the 16-bit MFMA as hi / lo parts) and, with it,
+    N.ATTN_OUT_SPLIT (out in the pre-split form a GEMM reads with A_SPLIT)."""
     _need(qkv, "qkv")
     W = heads * 64
     out = torch.empty(nseq * L, W, device=qkv.device, dtype=qkv.dtype)
     l = torch.empty(nseq * L, heads, device=qkv.device) if lse else None
-    N.call("clipk_attention_fwd", DT[qkv.dtype], nseq, L, heads, int(causal), _p(qkv), 3 * W, _p(out),
-           W, _p(l), _stream())
+    N.call("clipk_attention_fwd_ex", DT[qkv.dtype], nseq, L, heads, int(causal), _p(qkv), 3 * W, _p(out),
+           W, _p(l), int(flags), _stream())
     return (out, l) if lse else out
 
 

@@ -294,6 +294,23 @@ int clipk_layernorm_bwd_x2(int x_dtype, int dy_dtype, int rows, int width, const
  * out[(s*L+t), h*64+d]; lse[(s*L+t)*heads + h] (optional) = logsumexp of scaled scores. */
 int clipk_attention_fwd(int dtype, int nseq, int L, int heads, int causal,
                         const void* qkv, int ldqkv, void* out, int ldo, float* lse, void* stream);
+/* The same with flags (0: exactly clipk_attention_fwd):
+ * CLIPK_ATTN_SPLIT -- fp32 tensors on the 16-bit MFMA (PREC fp32s), any L > 16, causal or not: every
+ * operand element x is taken as hi = fp16(x), lo = fp16(x - hi) and every product (Q.K^T, P.V) as
+ * hi.hi + hi.lo + lo.hi with fp32 accumulation, the three-term rule of CLIPK_F32S; softmax, lse and
+ * 1 / l stay fp32. No range scaling: a part beyond fp16's range gives inf / NaN outputs. For
+ * L <= 16 the flagged call runs the exact-fp32 short kernel of the unflagged one.
+ * CLIPK_ATTN_OUT_SPLIT -- out is stored in the pre-split form of CLIPK_A_SPLIT (per 8 consecutive
+ * columns 16 B of hi parts, then 16 B of lo parts, of the fp32 o the call stores without the flag:
+ * bitwise the parts a split GEMM forms from it), for out_proj's A; lse is unchanged. Valid only
+ * together with CLIPK_ATTN_SPLIT, L > 16 and ldo % 8 == 0. clipk_attention_bwd reads o as fp32
+ * values: it must not be handed such an o.
+ * CLIPK_EINVAL, before any launch: a flag with a 16-bit dtype, CLIPK_ATTN_OUT_SPLIT outside the
+ * conditions above, an unknown bit. */
+enum { CLIPK_ATTN_SPLIT = 1, CLIPK_ATTN_OUT_SPLIT = 2 };
+int clipk_attention_fwd_ex(int dtype, int nseq, int L, int heads, int causal,
+                           const void* qkv, int ldqkv, void* out, int ldo, float* lse, int flags,
+                           void* stream);
 
 /* Input-grad backward of the attention core, any L (L <= 16: one MFMA tile; longer: two MFMA
  * passes, dK/dV per key tile and dQ per query tile; VALU for fp32): dqkv (grad_dtype) from qkv
