@@ -47,6 +47,9 @@ A_QGELU = 0x100  # OR-ed into epi: the GEMM consumes quickgelu(A) (include/clipk
 QGELU_DERIV = 0x200  # OR-ed into epi: out2 = quickgelu' (EPI_BIAS_QGELU) / aux is quickgelu' (EPI_DQGELU)
 OUT_SPLIT, A_SPLIT = 0x400, 0x800  # PREC fp32s pre-split operands (include/clipk.h)
 ADAM_ADAM, ADAM_ADAMW, ADAM_AMSGRAD = 0, 1, 2  # clipk_adam_step_multi modes
+# clipk_image_color op codes, program length and descriptor width (include/clipk.h)
+COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE = 1, 2, 3, 4, 5
+COLOR_MAX_OPS, COLOR_DESC = 5, 12
 PROF_NONE, PROF_GEMM_FC, PROF_GEMM_ALL, PROF_ATTN, PROF_LN, PROF_GEMM_DGELU = 0, 1, 2, 3, 4, 5
 
 _P = ctypes.c_void_p
@@ -80,6 +83,7 @@ SIGNATURES = {
     "clipk_gemm_ln_gamma": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     "clipk_gemm_ln_merge": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "clipk_image_resample": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "clipk_image_color": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
     "clipk_gemm_stamps": (_I, [_P, _S]),
     "clipk_layernorm_fwd": (_I, [_I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     "clipk_layernorm_bwd": (_I, [_I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P]),

@@ -1,6 +1,8 @@
 // Image preprocessing on the GPU: Pillow-exact bicubic resampling (two separable passes,
 // 22-bit fixed-point coefficients, uint8 rounding + clipping after each pass) over a crop
 // window, horizontal flip, and torchvision ToTensor + Normalize in fp32.
+// Colour stage (clipk_image_color, below): torchvision ColorJitter / RandomGrayscale on the
+// resampled uint8 pixels, Pillow-exact, one workgroup per image (arithmetic in color_ops.h).
 //
 // Replaces the Dassl/torchvision PIL transforms (Dassl.pytorch/dassl/data/transforms/
 // transforms.py:206-354: Resize + CenterCrop for test, RandomResizedCrop + flip for train)
@@ -8,7 +10,10 @@
 // precompute_coeffs + normalize_coeffs_8bpc) are built on the host in float64
 // (fsp_amd/data/preprocess.py); these kernels do the integer work. HBM/latency-bound: each
 // output pixel reads ~ksize source pixels per pass.
+#include <string.h>
+
 #include "common.h"
+#include "color_ops.h"
 
 namespace clipk {
 
@@ -85,6 +90,144 @@ __global__ __launch_bounds__(256) void resample_v_kernel(int B, int S, const lon
   }
 }
 
+// ---- colour stage (clipk_image_color) -------------------------------------------------------
+// One workgroup per image. Every lane owns the same groups of 4 consecutive pixels (group index
+// = lane, lane + 1024, ...) from the load to the epilogue, so the per-pixel ops of a program need
+// no barrier between them; CONTRAST, the one op that needs the whole image, takes its mean L from
+// an integer block reduction (order-independent) of the image as the ops before it left it.
+// LDS form: the three planes live in LDS (plane stride rounded up to 4 pixels, so a group is one
+// aligned dword per plane). In-place form (3 * S * S bytes do not fit): the same loop on the
+// caller's uint8 buffer. Groups that are not a whole aligned dword -- the tail of a plane when
+// S * S % 4 != 0, and any group of a misaligned plane in global memory -- move byte by byte.
+constexpr int kColorThreads = 1024;
+constexpr int kColorLdsBytes = 3 * 224 * 224;  // 150,528 B of the CU's 160 KiB; the rest: reduction
+
+__device__ __forceinline__ uint32_t px_load4(const uint8_t* p, int i, int n) {
+  if (i + 4 <= n && (((uintptr_t)(p + i)) & 3) == 0) return *reinterpret_cast<const uint32_t*>(p + i);
+  uint32_t v = 0;
+  for (int k = 0; k < 4; ++k)
+    if (i + k < n) v |= (uint32_t)p[i + k] << (8 * k);
+  return v;
+}
+
+__device__ __forceinline__ void px_store4(uint8_t* p, int i, int n, uint32_t v) {
+  if (i + 4 <= n && (((uintptr_t)(p + i)) & 3) == 0) {
+    *reinterpret_cast<uint32_t*>(p + i) = v;
+    return;
+  }
+  for (int k = 0; k < 4; ++k)
+    if (i + k < n) p[i + k] = (uint8_t)(v >> (8 * k));
+}
+
+// sum over the block of v (every lane gets it); red: one 64-bit slot per wave in LDS
+__device__ __forceinline__ unsigned long long color_block_sum(unsigned v, unsigned long long* red) {
+  unsigned long long w = v;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) w += __shfl_xor(w, o, 64);
+  __syncthreads();  // red may still be read from an earlier CONTRAST
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  unsigned long long t = 0;
+  for (int k = 0; k < kColorThreads / 64; ++k) t += red[k];
+  return t;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kColorThreads) void color_kernel(int S, uint8_t* __restrict__ pix,
+                                                              const int* __restrict__ prog,
+                                                              const float* __restrict__ mean,
+                                                              const float* __restrict__ stdv, int out_u8,
+                                                              void* __restrict__ out) {
+  __shared__ uint32_t s_img[LDS ? kColorLdsBytes / 4 : 1];
+  __shared__ unsigned long long s_red[kColorThreads / 64];
+  const int b = blockIdx.x;
+  const int n = S * S, ng = (n + 3) / 4;
+  uint8_t* src = pix + (size_t)b * 3 * n;
+  const int P = LDS ? ng * 4 : n;  // plane stride of the working copy
+  uint8_t* img = LDS ? reinterpret_cast<uint8_t*>(s_img) : src;
+  const int* pr = prog + (size_t)b * CLIPK_COLOR_DESC;
+  const int nops = pr[0];
+
+  if (LDS) {
+    for (int g = threadIdx.x; g < ng; g += kColorThreads)
+      for (int c = 0; c < 3; ++c) px_store4(img + c * P, 4 * g, n, px_load4(src + (size_t)c * n, 4 * g, n));
+  }
+
+  for (int k = 0; k < nops; ++k) {
+    const int op = pr[1 + k];
+    const int ip = pr[1 + CLIPK_COLOR_MAX_OPS + k];
+    const float f = __int_as_float(ip);
+    int d = 0;  // CONTRAST: the image's mean L, int(sum / count + 0.5)
+    if (op == CLIPK_COLOR_CONTRAST) {
+      unsigned part = 0;
+      for (int g = threadIdx.x; g < ng; g += kColorThreads) {
+        const uint32_t r4 = px_load4(img, 4 * g, n), g4 = px_load4(img + P, 4 * g, n),
+                       b4 = px_load4(img + 2 * P, 4 * g, n);
+        for (int j = 0; j < 4; ++j)
+          if (4 * g + j < n)
+            part += (unsigned)color::luma((r4 >> (8 * j)) & 255, (g4 >> (8 * j)) & 255, (b4 >> (8 * j)) & 255);
+      }
+      const unsigned long long sum = color_block_sum(part, s_red);
+      d = (int)((2 * sum + (unsigned long long)n) / (2 * (unsigned long long)n));
+    }
+    for (int g = threadIdx.x; g < ng; g += kColorThreads) {
+      const uint32_t r4 = px_load4(img, 4 * g, n), g4 = px_load4(img + P, 4 * g, n),
+                     b4 = px_load4(img + 2 * P, 4 * g, n);
+      uint32_t ro = 0, go = 0, bo = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        int r = (r4 >> (8 * j)) & 255, gg = (g4 >> (8 * j)) & 255, bb = (b4 >> (8 * j)) & 255;
+        switch (op) {  // uniform over the block
+          case CLIPK_COLOR_BRIGHTNESS:
+          case CLIPK_COLOR_CONTRAST:
+            r = color::blend(d, r, f), gg = color::blend(d, gg, f), bb = color::blend(d, bb, f);
+            break;
+          case CLIPK_COLOR_SATURATION: {
+            const int l = color::luma(r, gg, bb);
+            r = color::blend(l, r, f), gg = color::blend(l, gg, f), bb = color::blend(l, bb, f);
+            break;
+          }
+          case CLIPK_COLOR_HUE:
+            color::hue_shift(r, gg, bb, ip);
+            break;
+          default:  // CLIPK_COLOR_GRAYSCALE (the host admits no other code)
+            r = gg = bb = color::luma(r, gg, bb);
+            break;
+        }
+        ro |= (uint32_t)r << (8 * j), go |= (uint32_t)gg << (8 * j), bo |= (uint32_t)bb << (8 * j);
+      }
+      px_store4(img, 4 * g, n, ro);
+      px_store4(img + P, 4 * g, n, go);
+      px_store4(img + 2 * P, 4 * g, n, bo);
+    }
+  }
+
+  for (int g = threadIdx.x; g < ng; g += kColorThreads) {
+    const int i = 4 * g;
+    for (int c = 0; c < 3; ++c) {
+      const uint32_t v4 = px_load4(img + c * P, i, n);
+      const size_t o = ((size_t)b * 3 + c) * n;
+      if (out_u8) {
+        px_store4((uint8_t*)out + o, i, n, v4);
+      } else {
+        float* of = (float*)out + o;
+        float w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float t = (float)((v4 >> (8 * j)) & 255) / 255.0f;  // ToTensor: float().div(255)
+          w[j] = (t - mean[c]) / stdv[c];                           // Normalize: sub_(mean).div_(std)
+        }
+        if (i + 4 <= n && (((uintptr_t)(of + i)) & 15) == 0) {
+          store4(of + i, w[0], w[1], w[2], w[3]);
+        } else {
+          for (int j = 0; j < 4; ++j)
+            if (i + j < n) of[i + j] = w[j];
+        }
+      }
+    }
+  }
+}
+
 }  // namespace clipk
 
 using namespace clipk;
@@ -106,6 +249,42 @@ extern "C" int clipk_image_resample(int B, int S, int rows_max, const void* src,
   else
     hipLaunchKernelGGL(resample_v_kernel<false>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, B, S, desc,
                        tables, (const uint8_t*)tmp, mean, stdv, out);
+  CLIPK_CHECK_LAUNCH();
+  return CLIPK_OK;
+}
+
+extern "C" int clipk_image_color(int B, int S, void* pix, const int* prog, int* prog_dev, const float* mean,
+                                 const float* stdv, int out_uint8, void* out, void* stream) {
+  if (!pix || !prog || !prog_dev || !out || out == pix || (!out_uint8 && (!mean || !stdv))) return CLIPK_EINVAL;
+  if (B < 0 || S <= 0 || S > 4096) return CLIPK_ESHAPE;
+  for (int b = 0; b < B; ++b) {
+    const int* p = prog + (size_t)b * CLIPK_COLOR_DESC;
+    if (p[0] < 0 || p[0] > CLIPK_COLOR_MAX_OPS) return CLIPK_ESHAPE;
+    for (int k = 0; k < p[0]; ++k) {
+      const int op = p[1 + k], ip = p[1 + CLIPK_COLOR_MAX_OPS + k];
+      if (op == CLIPK_COLOR_BRIGHTNESS || op == CLIPK_COLOR_CONTRAST || op == CLIPK_COLOR_SATURATION) {
+        float f;
+        memcpy(&f, &ip, sizeof f);
+        if (!(f >= 0.0f) || f > 3.0e38f) return CLIPK_EINVAL;  // negative, NaN or inf
+      } else if (op == CLIPK_COLOR_HUE) {
+        if (ip < 0 || ip > 255) return CLIPK_EINVAL;
+      } else if (op != CLIPK_COLOR_GRAYSCALE) {
+        return CLIPK_EINVAL;
+      }
+    }
+  }
+  if (B == 0) return CLIPK_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // pageable host memory: staged before the call returns, so prog may be freed or reused at once
+  hipError_t e = hipMemcpyAsync(prog_dev, prog, (size_t)B * CLIPK_COLOR_DESC * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return (int)e;
+  const size_t n4 = ((size_t)S * S + 3) / 4 * 4;
+  if (3 * n4 <= (size_t)kColorLdsBytes)
+    hipLaunchKernelGGL(color_kernel<true>, dim3((unsigned)B), dim3(kColorThreads), 0, st, S, (uint8_t*)pix,
+                       (const int*)prog_dev, mean, stdv, out_uint8, out);
+  else
+    hipLaunchKernelGGL(color_kernel<false>, dim3((unsigned)B), dim3(kColorThreads), 0, st, S, (uint8_t*)pix,
+                       (const int*)prog_dev, mean, stdv, out_uint8, out);
   CLIPK_CHECK_LAUNCH();
   return CLIPK_OK;
 }

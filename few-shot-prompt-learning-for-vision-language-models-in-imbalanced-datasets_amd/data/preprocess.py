@@ -15,6 +15,14 @@ do the integer multiply-accumulate, the uint8 rounding/clipping of both passes, 
 window, the flip and ToTensor/Normalize in fp32 -- bit-exact to the PIL + torch pipeline
 (tests/test_preprocess_*.py check against Pillow itself).
 
+Colour augmentations (Dassl's ``colorjitter`` / ``randomgrayscale`` choices, and the SimCLR
+distortion ``RandomApply([ColorJitter], p) -> RandomGrayscale`` behind NATIVE.SIMCLR_COLOR): torchvision
+runs them on the PIL image after crop and flip, as thin wrappers over Pillow (ImageEnhance.*,
+convert("HSV"), convert("L")). Here each image carries a short program of ops, drawn on the host
+(``color_params``), and one more kernel (clipk_image_color) runs the programs on the resampled
+uint8 pixels and writes the normalised fp32 -- every byte Pillow's (tests/test_color_*.py). With
+no colour op configured nothing changes: the resample kernel writes fp32 directly.
+
 Random crop parameters and the flip coin use a torch CPU generator (the transform's own, or
 the global one) in torchvision's call order (RandomResizedCrop.get_params,
 RandomHorizontalFlip), restated here: torchvision is not installed, so that sequence is
@@ -104,13 +112,106 @@ def rrc_params(width, height, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), g
     return (height - h) // 2, (width - w) // 2, h, w
 
 
+def _jitter_range(value, name, center=1.0, bound=(0.0, float("inf")), clip_first_on_zero=True):
+    """torchvision ColorJitter._check_input: a number v -> [center - v, center + v] (the low end
+    clipped at 0 for brightness / contrast / saturation), a pair as given; None when the range is
+    the single point `center` (the component is off and draws nothing)."""
+    if isinstance(value, (int, float)) and not isinstance(value, bool):
+        if value < 0:
+            raise ValueError(f"If {name} is a single number, it must be non negative.")
+        value = [center - float(value), center + float(value)]
+        if clip_first_on_zero:
+            value[0] = max(value[0], 0.0)
+    elif isinstance(value, (tuple, list)) and len(value) == 2:
+        value = [float(value[0]), float(value[1])]
+    else:
+        raise TypeError(f"{name} should be a single number or a list/tuple with length 2.")
+    if not bound[0] <= value[0] <= value[1] <= bound[1]:
+        raise ValueError(f"{name} values should be between {bound}, but got {value}.")
+    if value[0] == value[1] == center:
+        return None
+    return tuple(value)
+
+
+def jitter_ranges(brightness=0, contrast=0, saturation=0, hue=0):
+    """ColorJitter.__init__: the four sampling ranges (None: component off). ValueError / TypeError
+    on what torchvision rejects (a negative number, a range outside [0, inf) or, for hue,
+    [-0.5, 0.5], a reversed pair)."""
+    return (_jitter_range(brightness, "brightness"), _jitter_range(contrast, "contrast"),
+            _jitter_range(saturation, "saturation"),
+            _jitter_range(hue, "hue", center=0.0, bound=(-0.5, 0.5), clip_first_on_zero=False))
+
+
+def hue_shift(hue_factor):
+    """torchvision adjust_hue's uint8 offset on Pillow's H channel, np.uint8(hue_factor * 255): the
+    product truncated toward zero, modulo 256."""
+    return int(hue_factor * 255) % 256
+
+
+def color_params(brightness=0, contrast=0, saturation=0, hue=0, generator=None):
+    """torchvision ColorJitter.get_params + forward as one image's colour program: torch.randperm(4)
+    first, then one torch.empty(1).uniform_(lo, hi) each for brightness, contrast, saturation and
+    hue in that order (a component whose range is off draws nothing) -> [(op, value), ...] in the
+    permuted order, value the blend factor (an fp32 value as a Python float) or, for COLOR_HUE, the
+    integer shift 0..255. Each argument: a number v (range [max(0, 1 - v), 1 + v]; hue [-v, v],
+    0 <= v <= 0.5), a (lo, hi) pair, or None (off)."""
+    ranges = jitter_ranges(*[0 if v is None else v for v in (brightness, contrast, saturation, hue)])
+    order = torch.randperm(4, generator=generator).tolist()
+    drawn = [None if r is None else float(torch.empty(1).uniform_(r[0], r[1], generator=generator)) for r in ranges]
+    ops_ = (N.COLOR_BRIGHTNESS, N.COLOR_CONTRAST, N.COLOR_SATURATION, N.COLOR_HUE)
+    prog = []
+    for k in order:
+        if drawn[k] is not None:
+            prog.append((ops_[k], hue_shift(drawn[k]) if k == 3 else drawn[k]))
+    return prog
+
+
+def pack_color_programs(programs):
+    """Host descriptors of clipk_image_color: int32 [B, COLOR_DESC] -- per image the op count, the op
+    codes in order, then their parameters (fp32 factor bits, or the hue shift)."""
+    desc = np.zeros((len(programs), N.COLOR_DESC), np.int32)
+    for b, prog in enumerate(programs):
+        prog = list(prog)
+        if len(prog) > N.COLOR_MAX_OPS:
+            raise ValueError(f"a colour program holds at most {N.COLOR_MAX_OPS} ops, got {len(prog)}")
+        desc[b, 0] = len(prog)
+        for k, (op, value) in enumerate(prog):
+            desc[b, 1 + k] = int(op)
+            if op in (N.COLOR_BRIGHTNESS, N.COLOR_CONTRAST, N.COLOR_SATURATION):
+                desc[b, 1 + N.COLOR_MAX_OPS + k] = np.array(value, np.float32).view(np.int32)
+            elif op == N.COLOR_HUE:
+                desc[b, 1 + N.COLOR_MAX_OPS + k] = int(value)
+    return desc
+
+
+def color_batch(pix, programs, mean=MEAN, std=STD, out_uint8=False):
+    """clipk_image_color on uint8 planar pixels [B, 3, S, S] (a CUDA tensor, contiguous): program b
+    runs on image b, then ToTensor + Normalize -> fp32 [B, 3, S, S], or the uint8 pixels when
+    out_uint8. One launch. `pix` is scratch: unspecified afterwards when the image does not fit LDS."""
+    if pix.dtype != torch.uint8 or pix.dim() != 4 or pix.shape[1] != 3 or pix.shape[2] != pix.shape[3]:
+        raise ValueError("pix must be uint8 [B, 3, S, S]")
+    if not pix.is_contiguous() or len(programs) != pix.shape[0]:
+        raise ValueError("pix must be contiguous, with one program per image")
+    B, S, dev = int(pix.shape[0]), int(pix.shape[2]), pix.device
+    desc = pack_color_programs(programs)
+    d_prog = torch.empty(max(B, 1) * N.COLOR_DESC, dtype=torch.int32, device=dev)
+    out = torch.empty(B, 3, S, S, device=dev, dtype=torch.uint8 if out_uint8 else torch.float32)
+    mean_t = torch.tensor(mean, dtype=torch.float32, device=dev)
+    std_t = torch.tensor(std, dtype=torch.float32, device=dev)
+    N.call("clipk_image_color", B, S, ops._p(pix), desc.ctypes.data, ops._p(d_prog), ops._p(mean_t), ops._p(std_t),
+           1 if out_uint8 else 0, ops._p(out), ops._stream())
+    return out
+
+
 class Plan:
     """One image's geometry: source window (x0, y0, w, h) resized to (rw, rh), output
-    window (ox, oy, S, S) of the resized image, horizontal flip."""
+    window (ox, oy, S, S) of the resized image, horizontal flip; `color`: the colour program
+    [(op, value), ...] that runs after them (empty: none)."""
 
-    def __init__(self, x0, y0, w, h, rw, rh, ox, oy, S, flip):
+    def __init__(self, x0, y0, w, h, rw, rh, ox, oy, S, flip, color=()):
         self.x0, self.y0, self.w, self.h = x0, y0, w, h
         self.rw, self.rh, self.ox, self.oy, self.S, self.flip = rw, rh, ox, oy, S, flip
+        self.color = list(color)
 
 
 def test_plan(w, h, size):
@@ -147,12 +248,16 @@ def _tables(plans, shapes):
     return np.asarray(desc, np.int64), np.concatenate(tabs).astype(np.int32), tmp_off
 
 
-def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8=False, src_index=None):
+def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8=False, src_index=None,
+                     color=None):
     """images: list of uint8 HWC (RGB) numpy arrays or CPU/GPU torch tensors; plans: Plan
     per image (all with the same S). Returns fp32 [B, 3, S, S] normalised on `device` (or
     the uint8 resampled pixels [B, 3, S, S] when out_uint8, for bit-exact checks).
     src_index: plans[k] reads images[src_index[k]] (B = len(plans) outputs from fewer source
-    images, each uploaded once: the two views of a SimCLR batch); None: plans[k] reads images[k]."""
+    images, each uploaded once: the two views of a SimCLR batch); None: plans[k] reads images[k].
+    color: one colour program per plan (color_params' form), run after crop and flip. When any is
+    non-empty the resample writes uint8 and clipk_image_color writes the output (one more launch);
+    None or all empty: the resample kernel writes the output itself, as without the argument."""
     dev = torch.device(device)
     S = plans[0].S
     if any(p.S != S for p in plans):
@@ -161,6 +266,10 @@ def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8
     for t in ts:
         if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
             raise ValueError("images must be uint8 [H, W, 3]")
+    color = None if color is None else [list(c) for c in color]
+    if color is not None and len(color) != len(plans):
+        raise ValueError("color must hold one program per plan")
+    staged = color is not None and any(color)
     src_index = [int(k) for k in (range(len(plans)) if src_index is None else src_index)]
     if len(src_index) != len(plans) or any(not 0 <= k < len(ts) for k in src_index):
         raise ValueError("src_index must name one source image per plan")
@@ -177,22 +286,31 @@ def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8
     d_tab = torch.from_numpy(tab).to(dev)
     tmp = torch.empty(max(tmp_elems, 1), dtype=torch.uint8, device=dev)
     B = len(plans)
-    out = torch.empty(B, 3, S, S, device=dev, dtype=torch.uint8 if out_uint8 else torch.float32)
+    to_u8 = out_uint8 or staged
+    out = torch.empty(B, 3, S, S, device=dev, dtype=torch.uint8 if to_u8 else torch.float32)
     mean_t = torch.tensor(mean, dtype=torch.float32, device=dev)
     std_t = torch.tensor(std, dtype=torch.float32, device=dev)
     rows_max = int(desc[:, 11].max())
     N.call("clipk_image_resample", B, S, rows_max, ops._p(src), ops._p(d_desc), ops._p(d_tab), ops._p(tmp),
-           ops._p(mean_t), ops._p(std_t), 1 if out_uint8 else 0, ops._p(out), ops._stream())
+           ops._p(mean_t), ops._p(std_t), 1 if to_u8 else 0, ops._p(out), ops._stream())
+    if staged:
+        return color_batch(out, color, mean, std, out_uint8)
     return out
 
 
 class GpuTransform:
     """Dassl transform_train / transform_test equivalent for the CoOp/CoCoOp configs
-    (random_resized_crop + random_flip + normalize / resize + center_crop + normalize)."""
+    (random_resized_crop + random_flip + normalize / resize + center_crop + normalize), plus
+    Dassl's colorjitter (ColorJitter(INPUT.COLORJITTER_B/C/S/H), under RandomApply when
+    INPUT.COLORJITTER_P < 1) and randomgrayscale (RandomGrayscale(INPUT.RGS_P)) for training, in
+    the reference's order: crop, flip, colour, grayscale, ToTensor, Normalize. With
+    NATIVE.SIMCLR_COLOR and a two-view objective (data/manager.py two_views) the training transform
+    carries the SimCLR distortion whatever INPUT.TRANSFORMS says: the jitter under
+    RandomApply(NATIVE.SIMCLR_COLOR_P), then RandomGrayscale(INPUT.RGS_P)."""
 
     def __init__(self, cfg, is_train, device="cuda", generator=None):
         choices = list(cfg.INPUT.TRANSFORMS)
-        allowed = {"random_resized_crop", "random_flip", "normalize"}
+        allowed = {"random_resized_crop", "random_flip", "normalize", "colorjitter", "randomgrayscale"}
         if is_train and not set(choices) <= allowed:
             raise NotImplementedError(f"GPU transforms implement {sorted(allowed)}, got {choices}")
         if cfg.INPUT.INTERPOLATION != "bicubic":
@@ -207,16 +325,44 @@ class GpuTransform:
         self.std = tuple(cfg.INPUT.PIXEL_STD) if norm else (1.0, 1.0, 1.0)
         self.device = device
         self.generator = generator  # None: torch's global CPU RNG
+        # colour stage (training only): jitter ranges (None: no jitter), the RandomApply probability
+        # around it (>= 1: no coin is drawn) and RandomGrayscale's probability (None: not configured)
+        self.jitter, self.jitter_p, self.gray_p = None, 1.0, None
+        if is_train:
+            from .manager import two_views
+            simclr = bool(cfg.get("NATIVE", {}).get("SIMCLR_COLOR", False)) and two_views(cfg)
+            if simclr or "colorjitter" in choices:
+                inp = cfg.INPUT
+                self.jitter = jitter_ranges(inp.get("COLORJITTER_B", 0.4), inp.get("COLORJITTER_C", 0.4),
+                                            inp.get("COLORJITTER_S", 0.4), inp.get("COLORJITTER_H", 0.1))
+                self.jitter_p = float(cfg.NATIVE.get("SIMCLR_COLOR_P", 0.8) if simclr
+                                      else cfg.INPUT.get("COLORJITTER_P", 1.0))
+            if simclr or "randomgrayscale" in choices:
+                self.gray_p = float(cfg.INPUT.get("RGS_P", 0.2))
+
+    def color_program(self):
+        """One image's colour draws, after its crop and flip: the RandomApply coin (torch.rand(1);
+        skipped when p < coin) when jitter_p < 1, the jitter draws (color_params), the grayscale
+        coin (torch.rand(1) < p). Draws nothing when no colour op is configured."""
+        prog = []
+        if self.jitter is not None:
+            if not (self.jitter_p < 1.0 and self.jitter_p < float(torch.rand(1, generator=self.generator))):
+                prog += color_params(*self.jitter, generator=self.generator)
+        if self.gray_p is not None and bool(torch.rand(1, generator=self.generator) < self.gray_p):
+            prog.append((N.COLOR_GRAYSCALE, 0))
+        return prog
 
     def plan(self, w, h):
         if not self.is_train:
             return test_plan(w, h, self.size)
         if self.rrc:
-            return train_plan(w, h, self.size, self.scale, 0.5 if self.flip else 0.0, generator=self.generator)
-        rw = rh = self.size  # Resize(input_size) when no random crop
-        p = Plan(0, 0, w, h, rw, rh, 0, 0, self.size, False)
-        if self.flip:
-            p.flip = bool(torch.rand(1, generator=self.generator) < 0.5)
+            p = train_plan(w, h, self.size, self.scale, 0.5 if self.flip else 0.0, generator=self.generator)
+        else:
+            rw = rh = self.size  # Resize(input_size) when no random crop
+            p = Plan(0, 0, w, h, rw, rh, 0, 0, self.size, False)
+            if self.flip:
+                p.flip = bool(torch.rand(1, generator=self.generator) < 0.5)
+        p.color = self.color_program()
         return p
 
     def plans(self, sizes, views=1):
@@ -227,14 +373,17 @@ class GpuTransform:
     def __call__(self, images, views=1):
         """views=1: the transformed batch [B, 3, S, S]. views=2 (SimCLR): two independent draws of
         the transform per image -> (x1, x2), the two halves of ONE [2B, 3, S, S] output (no copy);
-        the pixels are uploaded once and one resample launch covers both views."""
+        the pixels are uploaded once and one resample launch (and, with colour ops, one colour launch)
+        covers both views."""
         sizes = [(int(im.shape[1]), int(im.shape[0])) for im in images]
         if views == 1:
-            return preprocess_batch(images, self.plans(sizes), self.mean, self.std, self.device)
+            drawn = self.plans(sizes)
+            return preprocess_batch(images, drawn, self.mean, self.std, self.device, color=[p.color for p in drawn])
         if views != 2:
             raise ValueError(f"views must be 1 or 2, got {views}")
         B = len(sizes)
         drawn = self.plans(sizes, 2)  # image-major
-        out = preprocess_batch(images, drawn[0::2] + drawn[1::2], self.mean, self.std, self.device,
-                               src_index=list(range(B)) * 2)
+        drawn = drawn[0::2] + drawn[1::2]
+        out = preprocess_batch(images, drawn, self.mean, self.std, self.device, src_index=list(range(B)) * 2,
+                               color=[p.color for p in drawn])
         return out[:B], out[B:]

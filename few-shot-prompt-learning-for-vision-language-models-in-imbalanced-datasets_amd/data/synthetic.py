@@ -32,8 +32,10 @@ MIX_SEED = 700_000  # offset of the mixup stream's seed (mixup_alpha)
 class SyntheticDataManager:
     def __init__(self, n_cls, resolution, batch_size, n_batches=2, test_batch=100, n_test=0,
                  per_class_shots=None, device="cuda", seed=1, rank=0, n_test_device=0, two_views=False,
-                 mixup_alpha=None):
-        """mixup_alpha (not None): every training batch is mixed as data/manager.py GpuLoader mixes
+                 mixup_alpha=None, simclr_color=False):
+        """simclr_color (NATIVE.SIMCLR_COLOR of the real loader): rejected -- the synthetic images are
+        normalised noise, not uint8 pixels a colour op is defined on.
+        mixup_alpha (not None): every training batch is mixed as data/manager.py GpuLoader mixes
         them (draw_mix from a generator seeded MIX_SEED + seed + 7919 * rank, one draw per batch in
         batch order; ops.mixup_images): "img" the mixed images, "y_a" (= "label", kept), "y_b",
         "lam" (a Python float). Not together with two_views.
@@ -47,6 +49,9 @@ class SyntheticDataManager:
         SURVEY §8(d) -- 30 GB at 224 px fp32, resident, every image distinct."""
         if two_views and mixup_alpha is not None:
             raise ValueError("two_views batches are not mixed")
+        if simclr_color:
+            raise ValueError("synthetic views are normalised noise, not uint8 pixels: the colour distortion "
+                             "(NATIVE.SIMCLR_COLOR) needs the DataManager's GPU transform")
         self.dataset = _Dataset(synth.synthetic_classnames(n_cls))
         dev = torch.device(device)
         rs = np.random.RandomState(1000 + seed + 7919 * rank)

@@ -100,7 +100,14 @@ def get_cfg_default() -> CfgNode:
         "INPUT": {"SIZE": (224, 224), "INTERPOLATION": "bicubic",
                   "PIXEL_MEAN": [0.48145466, 0.4578275, 0.40821073],
                   "PIXEL_STD": [0.26862954, 0.26130258, 0.27577711],
-                  "TRANSFORMS": ["random_resized_crop", "random_flip", "normalize"]},
+                  "TRANSFORMS": ["random_resized_crop", "random_flip", "normalize"],
+                  # the colorjitter / randomgrayscale choices of TRANSFORMS (training only;
+                  # data/preprocess.py). The strengths and RGS_P follow Dassl's defaults as this
+                  # package defines them (the reference's defaults.py is not pinned); COLORJITTER_P
+                  # is this package's: the probability of a RandomApply around the jitter (1.0: the
+                  # bare ColorJitter, no coin drawn)
+                  "COLORJITTER_B": 0.4, "COLORJITTER_C": 0.4, "COLORJITTER_S": 0.4, "COLORJITTER_H": 0.1,
+                  "COLORJITTER_P": 1.0, "RGS_P": 0.2},
         "DATASET": {"ROOT": "", "NAME": "", "NUM_SHOTS": -1, "PER_CLASS_SHOTS": [],
                     "SUBSAMPLE_CLASSES": "all"},
         "DATALOADER": {"NUM_WORKERS": 8, "TRAIN_X": {"SAMPLER": "RandomSampler", "BATCH_SIZE": 32},
@@ -171,6 +178,12 @@ def get_cfg_default() -> CfgNode:
                    # ONE encode of the class prompts instead of one per view. Off: the torch
                    # composition and the reference's two forward_once calls, bit for bit as before
                    "FUSED_SIMCLR": False,
+                   # SIMCLR_COLOR: the two views of a SimCLR objective (data/manager.py two_views)
+                   # also get the SimCLR colour distortion, whatever INPUT.TRANSFORMS says:
+                   # RandomApply([ColorJitter(INPUT.COLORJITTER_*)], SIMCLR_COLOR_P), then
+                   # RandomGrayscale(INPUT.RGS_P), on the GPU (clipk_image_color). Off: the views are
+                   # two draws of crop + flip, bit for bit as before
+                   "SIMCLR_COLOR": False, "SIMCLR_COLOR_P": 0.8,
                    # MIXUP: IVLP trains on mixed batches as the reference's default run does
                    # (TRAINER.IVLP.USE_MIXUP / MIXUP_ALPHA): the training loader mixes every batch
                    # (clipk_mixup_images; "y_a" / "y_b" / "lam") and the mixed criterion is one native

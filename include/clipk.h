@@ -236,6 +236,29 @@ int clipk_image_resample(int B, int S, int rows_max, const void* src, const long
                          const int* tables, void* tmp, const float* mean, const float* stdv,
                          int out_uint8, void* out, void* stream);
 
+/* Colour augmentations on the resampled pixels (torchvision ColorJitter / RandomGrayscale on PIL
+ * images, i.e. Pillow's ImageEnhance.Brightness / Contrast / Color, convert("HSV") and convert("L");
+ * csrc/preprocess.hip "colour stage", DESIGN §3 "Colour kernels"): every uint8 result is Pillow's.
+ * pix: uint8 planar [B,3,S,S], what clipk_image_resample(out_uint8 = 1) writes. prog: HOST int32
+ * [B, CLIPK_COLOR_DESC] -- per image [0] the number of ops n (0..CLIPK_COLOR_MAX_OPS), [1..5] the
+ * op codes in the order they run, [6..10] their parameters (the bits of the fp32 blend factor for
+ * BRIGHTNESS / CONTRAST / SATURATION, the integer shift 0..255 for HUE, unused for GRAYSCALE), [11]
+ * zero. The call checks prog on the host, then copies it to prog_dev (device, B * CLIPK_COLOR_DESC
+ * * 4 bytes, caller-owned) on the stream and launches ONE kernel. out: fp32 [B,3,S,S] =
+ * ((float)v / 255.0f - mean[c]) / stdv[c], the expression of clipk_image_resample's epilogue (an
+ * image with n = 0 is bitwise that call's out_uint8 = 0 output), or the uint8 pixels when out_uint8.
+ * One workgroup per image; the image lives in LDS while its program runs when 3 * S * S bytes fit
+ * (S <= 224), otherwise the same code runs in place in pix, whose contents are then unspecified
+ * afterwards. out must not be pix. B == 0: CLIPK_OK, nothing launched. CLIPK_EINVAL: pix, prog,
+ * prog_dev or out null, mean / stdv null without out_uint8, out == pix, an unknown op code, a blend
+ * factor that is negative or not finite, a shift outside 0..255; CLIPK_ESHAPE: B < 0, S <= 0, S >
+ * 4096, n outside 0..CLIPK_COLOR_MAX_OPS. */
+enum { CLIPK_COLOR_BRIGHTNESS = 1, CLIPK_COLOR_CONTRAST = 2, CLIPK_COLOR_SATURATION = 3,
+       CLIPK_COLOR_HUE = 4, CLIPK_COLOR_GRAYSCALE = 5 };
+enum { CLIPK_COLOR_MAX_OPS = 5, CLIPK_COLOR_DESC = 12 };
+int clipk_image_color(int B, int S, void* pix, const int* prog, int* prog_dev, const float* mean,
+                      const float* stdv, int out_uint8, void* out, void* stream);
+
 /* Diagnostic: per-block / per-tile s_memrealtime marks of the last GEMM launch, recorded
  * only when the process runs with CLIPK_GEMM_STAMP set (synchronises the device). */
 int clipk_gemm_stamps(void* host, size_t bytes);

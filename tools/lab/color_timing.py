@@ -1,0 +1,120 @@
+"""Times the colour stage of the SimCLR views on the GPU (DESIGN section 5 "Colour views").
+
+  python tools/lab/color_timing.py [--out profiles/color/timing.json] [--skip-step]
+
+* clipk_image_color alone at B = 64, S = 224 (uint8 in, normalised fp32 out; the descriptor
+  packing and its copy included, as every call pays them): the full five-op program, the same
+  program without contrast (no image-wide reduction), and an empty program (load + epilogue only);
+* the two-view GpuTransform call (32 decoded images of 500 x 375 -> two views of 224 x 224: upload,
+  resample, and with the flag the colour launch) with NATIVE.SIMCLR_COLOR off and on;
+* the CoOp SimCLR train step at the shapes of DESIGN section 5 "SimCLR" (ViT-B/16, C = 1000,
+  B = 32, n_ctx 16, FUSED_SIMCLR on) fed by that transform call, flag off and on.
+
+Each variant runs `--iters` calls per block between two synchronises (host clock), the variants
+alternate block by block in one process for `--rounds` rounds, and the median block is reported
+with its min and max (the run-to-run spread the on / off difference has to be read against).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def timed(variants, iters, rounds, warm=3, unit=1e6):
+    for fn in variants.values():  # warm-up: code objects, allocator
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    blocks = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                fn()
+            torch.cuda.synchronize()
+            blocks[k].append((time.perf_counter() - t0) / iters * unit)
+    return {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in blocks.items()}
+
+
+def transform(flag, dev, seed=0):
+    from fsp_amd.data.preprocess import GpuTransform
+    from fsp_amd.engine.config import get_cfg_default
+    cfg = get_cfg_default()
+    cfg.TRAINER.NAME = "CoOp"
+    cfg.TRAINER.COOP.LOSS_TYPE = "simclr"
+    cfg.NATIVE.SIMCLR_COLOR = flag
+    g = torch.Generator()
+    g.manual_seed(seed)
+    return GpuTransform(cfg, is_train=True, device=dev, generator=g)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--prec", default="fp32s")
+    ap.add_argument("--skip-step", action="store_true")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("color_timing.py needs the GPU: nothing is measured without one")
+    from fsp_amd import _native as N
+    from fsp_amd.data import preprocess as P
+    dev = torch.device("cuda:0")
+    res = {"device": torch.cuda.get_device_name(0), "iters": args.iters, "rounds": args.rounds}
+
+    # 1. the kernel alone
+    B, S = 64, 224
+    rs = np.random.RandomState(0)
+    pix = torch.from_numpy(rs.randint(0, 256, size=(B, 3, S, S), dtype=np.uint8)).to(dev)
+    f = [float(np.float32(v)) for v in (1.2, 0.8, 1.3)]
+    five = [(N.COLOR_BRIGHTNESS, f[0]), (N.COLOR_CONTRAST, f[1]), (N.COLOR_SATURATION, f[2]), (N.COLOR_HUE, 17),
+            (N.COLOR_GRAYSCALE, 0)]
+    progs = {"five_ops": five, "no_contrast": [op for op in five if op[0] != N.COLOR_CONTRAST], "empty": []}
+    r = timed({k: (lambda p=p: P.color_batch(pix, [p] * B)) for k, p in progs.items()}, args.iters, args.rounds)
+    nbytes = B * 3 * S * S * (1 + 4)  # uint8 read, fp32 write
+    for v in r.values():
+        v["GBps_at_median"] = nbytes / v["median"] * 1e-3
+    res["kernel_us_B64_S224"] = dict(r, bytes=nbytes)
+
+    # 2. the two-view transform call
+    images = [rs.randint(0, 256, size=(375, 500, 3), dtype=np.uint8) for _ in range(32)]
+    tf = {"off": transform(False, dev), "on": transform(True, dev)}
+    res["two_view_transform_us_B32"] = timed({k: (lambda t=t: t(images, views=2)) for k, t in tf.items()},
+                                             max(args.iters // 5, 5), args.rounds)
+
+    # 3. the training step fed by it
+    if not args.skip_step:
+        import simclr_step
+        torch.manual_seed(0)
+        tr, _ = simclr_step.coop_trainer(args.prec, True, dev)
+        labels = torch.from_numpy(rs.randint(0, 1000, size=32).astype(np.int64)).to(dev)
+
+        def step(t):
+            x1, x2 = t(images, views=2)
+            tr.forward_backward({"img": x1, "img1": x1, "img2": x2, "label": labels})
+
+        res["coop_simclr_step_ms"] = dict(
+            timed({k: (lambda t=t: step(t)) for k, t in tf.items()}, args.steps, args.rounds, warm=2, unit=1e3),
+            shapes="ViT-B/16 C 1000 B 32 n_ctx 16 %s FUSED_SIMCLR, transform call included" % args.prec)
+
+    text = json.dumps(res, indent=1)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
