@@ -50,6 +50,7 @@ ADAM_ADAM, ADAM_ADAMW, ADAM_AMSGRAD = 0, 1, 2  # clipk_adam_step_multi modes
 # clipk_image_color op codes, program length and descriptor width (include/clipk.h)
 COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE = 1, 2, 3, 4, 5
 COLOR_MAX_OPS, COLOR_DESC = 5, 12
+CONV_RES, CONV_RELU, CONV_OUT_F32 = 1, 2, 4  # clipk_conv2d_nhwc flags
 PROF_NONE, PROF_GEMM_FC, PROF_GEMM_ALL, PROF_ATTN, PROF_LN, PROF_GEMM_DGELU = 0, 1, 2, 3, 4, 5
 
 _P = ctypes.c_void_p
@@ -163,6 +164,15 @@ SIGNATURES = {
     "clipk_vision_create": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "clipk_vit_ws_bytes": (_S, [_P, _I]),
     "clipk_vit_forward": (_I, [_P, _I, _P, _P, _P, _S, _P]),
+    "clipk_conv2d_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "clipk_im2col_3x3s2": (_I, [_I, _I, _I, _P, _P, _P]),
+    "clipk_avgpool2_nhwc": (_I, [_I, _I, _I, _I, _I, _P, _P, _P]),
+    "clipk_attnpool_ws_bytes": (_S, [_I, _I, _I, _I]),
+    "clipk_attnpool": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _S, _P]),
+    "clipk_resnet_create": (_I, [_I, _P, _I, _I, _I, _P, _I, _P]),
+    "clipk_resnet_destroy": (None, [_P]),
+    "clipk_resnet_ws_bytes": (_S, [_P, _I]),
+    "clipk_resnet_forward": (_I, [_P, _I, _P, _P, _P, _S, _P]),
     "clipk_prof_enable": (_I, [_I]),
     "clipk_prof_read": (_I, [_P, _P, _P]),
     "clipk_prof_sites_enable": (_I, [_I]),

@@ -5,6 +5,8 @@ Mirrors the pieces of ``PromptSRC/clip/model.py`` that the CoOp/CoCoOp trainers 
 ``positional_embedding``, ``ln_final``, ``text_projection``, ``logit_scale``, ``dtype``),
 but the encoders run as libclipk.so launch sequences:
 
+* ``ResNetEncoder``  — ModifiedResNet.forward (model.py:94-150; RN50 / RN101), frozen and
+  forward-only, on the MFMA convolutions of csrc/conv.hip.
 * ``VisionEncoder``  — VisionTransformer.forward (model.py:401-431), frozen; with
   ``with_grad`` also the prompted ViT of IVLP / MaPLe / PromptSRC (visual prompt rows after the
   image tokens + deep prompts, model.py:191-331, 434-485) with its input-grad backward,
@@ -94,21 +96,32 @@ def _t(v):
     return torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v.detach()
 
 
+def _text_arch(sd):
+    W = _t(sd["ln_final.weight"]).shape[0]
+    tl = len({k.split(".")[2] for k in sd if k.startswith("transformer.resblocks")})
+    return dict(embed_dim=_t(sd["text_projection"]).shape[1], context_length=_t(sd["positional_embedding"]).shape[0],
+                vocab_size=_t(sd["token_embedding.weight"]).shape[0], transformer_width=W,
+                transformer_heads=W // 64, transformer_layers=tl)
+
+
 def arch_from_state_dict(sd) -> ClipArch:
-    """Infer the ViT CLIP shape from state-dict shapes (model.py:663-687)."""
+    """Infer the CLIP shape from state-dict shapes (model.py:663-687): a ViT (``visual.proj``), or
+    a ModifiedResNet (no ``visual.proj``, ``visual.attnpool.*``), whose ``vision_layers`` is the
+    tuple of block counts and ``vision_patch_size`` None, as build_model's."""
     if "visual.proj" not in sd:
-        raise KeyError("only ViT CLIP backbones are on this path (ModifiedResNet is out of scope)")
+        if "visual.attnpool.positional_embedding" not in sd:
+            raise KeyError("neither a ViT (visual.proj) nor a ModifiedResNet (visual.attnpool.*) CLIP state dict")
+        counts = tuple(len({k.split(".")[2] for k in sd if k.startswith(f"visual.layer{b}.")}) for b in (1, 2, 3, 4))
+        S = round((_t(sd["visual.attnpool.positional_embedding"]).shape[0] - 1) ** 0.5)
+        return ClipArch(image_resolution=32 * S, vision_layers=counts,
+                        vision_width=_t(sd["visual.layer1.0.conv1.weight"]).shape[0], vision_patch_size=None,
+                        **_text_arch(sd))
     D = _t(sd["visual.conv1.weight"]).shape[0]
     layers = len([k for k in sd if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
     p = _t(sd["visual.conv1.weight"]).shape[-1]
     grid = round((_t(sd["visual.positional_embedding"]).shape[0] - 1) ** 0.5)
-    W = _t(sd["ln_final.weight"]).shape[0]
-    tl = len({k.split(".")[2] for k in sd if k.startswith("transformer.resblocks")})
-    return ClipArch(embed_dim=_t(sd["text_projection"]).shape[1], image_resolution=p * grid,
-                    vision_layers=layers, vision_width=D, vision_patch_size=p,
-                    context_length=_t(sd["positional_embedding"]).shape[0],
-                    vocab_size=_t(sd["token_embedding.weight"]).shape[0], transformer_width=W,
-                    transformer_heads=W // 64, transformer_layers=tl)
+    return ClipArch(image_resolution=p * grid, vision_layers=layers, vision_width=D, vision_patch_size=p,
+                    **_text_arch(sd))
 
 
 class _Workspace:
@@ -859,6 +872,117 @@ class LoraVisionFn(torch.autograd.Function):
         return dA, dB, None, None
 
 
+VIT_ONLY_TRAINERS = ("IVLP", "MaPLe", "PromptSRC", "LoRA")
+
+
+def require_vit(trainer: str, backbone: str, arch: ClipArch):
+    """IVLP, MaPLe and PromptSRC put prompt rows into a ViT and LoRA adapts transformer blocks: with a
+    ModifiedResNet backbone they raise, naming it."""
+    if arch.is_resnet:
+        raise ValueError(f"{trainer} needs a ViT image encoder (visual prompt rows / transformer blocks); backbone "
+                         f"{backbone!r} is a ModifiedResNet with blocks {tuple(arch.vision_layers)}. CoOp, CoCoOp, "
+                         f"ZeroshotCLIP, ZeroshotCLIP2 and LinearProbeCLIP run on it.")
+
+
+def bn_affine(sd, key):
+    """Frozen BatchNorm (eval) as y = x * scale + shift, fp32 (formed in fp64):
+    scale = weight / sqrt(running_var + 1e-5), shift = bias - running_mean * scale."""
+    g = lambda n: _t(sd[f"{key}.{n}"]).double()
+    scale = g("weight") / torch.sqrt(g("running_var") + 1e-5)
+    shift = g("bias") - g("running_mean") * scale
+    return scale.float(), shift.float()
+
+
+def conv_pack(w, kpad=None):
+    """Conv2d weight [Cout, Cin, k, k] -> the implicit GEMM's [Cout, k*k*Cin] (tap-major, channel
+    fastest; clipk_conv2d_nhwc), zero padded to kpad columns."""
+    w = _t(w).float()
+    out = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+    if kpad is not None and out.shape[1] < kpad:
+        out = torch.cat([out, torch.zeros(out.shape[0], kpad - out.shape[1])], 1)
+    return out.contiguous()
+
+
+class ResNetEncoder(nn.Module):
+    """ModifiedResNet image encoder (RN50 / RN101, model.py:94-150) on the native path: image
+    [B,3,R,R] fp32 -> [B,E] fp32 through clipk_resnet_forward. Frozen and forward-only. PREC fp16 /
+    bf16 / amp run the tower in the act dtype; fp32 and fp32s both on the f32 MFMA."""
+
+    def __init__(self, sd, arch: ClipArch, prec: str, device):
+        nn.Module.__init__(self)
+        act, _ = PREC_DTYPES[prec]
+        self.arch, self.act, self.dev = arch, act, torch.device(device)
+        self.input_resolution = arch.image_resolution
+        self.output_dim = arch.embed_dim
+        self.lora = None
+        f32 = lambda x: _t(x).float().to(self.dev).contiguous()
+        A = lambda x: x.to(self.dev, act).contiguous()
+        table = []
+
+        def conv_bn(conv, bn, kpad=None):
+            scale, shift = bn_affine(sd, bn)
+            table.extend([A(conv_pack(sd[conv + ".weight"], kpad)), f32(scale), f32(shift)])
+
+        conv_bn("visual.conv1", "visual.bn1", kpad=32)
+        conv_bn("visual.conv2", "visual.bn2")
+        conv_bn("visual.conv3", "visual.bn3")
+        for l, n in enumerate(arch.vision_layers, 1):
+            for i in range(n):
+                p = f"visual.layer{l}.{i}."
+                for j in (1, 2, 3):
+                    conv_bn(p + f"conv{j}", p + f"bn{j}")
+                if p + "downsample.0.weight" in sd:
+                    conv_bn(p + "downsample.0", p + "downsample.1")
+                else:
+                    table.extend([None, None, None])
+        ap = "visual.attnpool."
+        w = lambda n: _t(sd[ap + n]).float()
+        table += [f32(w("positional_embedding")), A(w("q_proj.weight")), f32(w("q_proj.bias")),
+                  A(torch.cat([w("k_proj.weight"), w("v_proj.weight")], 0)),
+                  f32(torch.cat([w("k_proj.bias"), w("v_proj.bias")], 0)),
+                  A(w("c_proj.weight")), f32(w("c_proj.bias"))]
+        self._keep = table
+        self.handle = None
+        h = ctypes.c_void_p()
+        blocks = (ctypes.c_int * 4)(*arch.vision_layers)
+        N.check(N.load().clipk_resnet_create(arch.vision_width, blocks, arch.embed_dim, arch.image_resolution,
+                                             ops.DT[act], _ptrs(table), len(table), ctypes.byref(h)),
+                "clipk_resnet_create")
+        self.handle = h
+
+    def _check_image(self, image):
+        image = image.to(self.dev, torch.float32).contiguous()
+        if image.shape[1:] != (3, self.input_resolution, self.input_resolution):
+            raise RuntimeError(f"expected [B,3,{self.input_resolution},{self.input_resolution}] images, "
+                               f"got {tuple(image.shape)}")
+        return image
+
+    def forward_prompted(self, *args, **kwargs):
+        raise ValueError("a ModifiedResNet image encoder has no token rows for visual prompts (ViT backbones only)")
+
+    def forward(self, image):
+        if image.requires_grad:
+            raise RuntimeError("the image encoder is frozen and forward-only (no input grad)")
+        image = self._check_image(image)
+        B = image.shape[0]
+        lib = N.load()
+        feat = torch.empty(B, self.output_dim, device=self.dev)
+        wsb = lib.clipk_resnet_ws_bytes(self.handle, B)
+        ws = WORKSPACE.get(wsb, self.dev, "resnet")
+        N.check(lib.clipk_resnet_forward(self.handle, B, ops._p(image), ops._p(feat), ops._p(ws), ws.numel(),
+                                         ops._stream()), "clipk_resnet_forward")
+        return feat
+
+    def __del__(self):
+        h = self.__dict__.get("handle")
+        if h is not None:
+            self.__dict__["handle"] = None  # not nn.Module.__setattr__: it may be gone at shutdown
+            try:
+                N.load().clipk_resnet_destroy(h)
+            except Exception:
+                pass
+
+
 class CLIP(nn.Module):
     """Container with the attributes the prompt learners read (model.py:488-561)."""
 
@@ -870,7 +994,14 @@ class CLIP(nn.Module):
         arch = arch_from_state_dict(sd)
         self.arch, self.prec = arch, prec
         dev = torch.device(device)
-        self.visual = VisionEncoder(sd, arch, prec, dev, with_grad=vision_grad, lora=vision_lora, ln_fold=ln_fold)
+        if arch.is_resnet:
+            if vision_grad or vision_lora is not None:
+                raise ValueError("a ModifiedResNet image encoder is frozen and forward-only: vision_grad / "
+                                 "vision_lora need a ViT backbone")
+            self.visual = ResNetEncoder(sd, arch, prec, dev)
+        else:
+            self.visual = VisionEncoder(sd, arch, prec, dev, with_grad=vision_grad, lora=vision_lora,
+                                        ln_fold=ln_fold)
         self.text = TextEncoderCore(sd, arch, prec, dev, with_grad=text_grad, lora=text_lora, ln_fold=ln_fold)
         W = arch.transformer_width
         self.token_embedding = nn.Embedding(arch.vocab_size, W)

@@ -31,9 +31,9 @@ CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 class ClipArch:
     embed_dim: int
     image_resolution: int
-    vision_layers: int
+    vision_layers: int | tuple  # ViT: layers; ModifiedResNet: the four block counts
     vision_width: int
-    vision_patch_size: int
+    vision_patch_size: int | None  # None: ModifiedResNet
     context_length: int
     vocab_size: int
     transformer_width: int
@@ -41,8 +41,12 @@ class ClipArch:
     transformer_layers: int
 
     @property
-    def vision_heads(self) -> int:  # model.py:506 (ViT branch)
-        return self.vision_width // 64
+    def is_resnet(self) -> bool:  # model.py:503 (vision_layers a tuple: ModifiedResNet)
+        return isinstance(self.vision_layers, (tuple, list))
+
+    @property
+    def vision_heads(self) -> int:  # model.py:504 / 506
+        return self.vision_width * 32 // 64 if self.is_resnet else self.vision_width // 64
 
     @property
     def grid(self) -> int:
@@ -65,13 +69,103 @@ ARCHS = {
     "tiny": ClipArch(128, 32, 2, 128, 16, 77, 49408, 128, 2, 2),
     "tiny-p8": ClipArch(128, 32, 2, 128, 8, 77, 49408, 128, 2, 2),
     "tiny4": ClipArch(128, 32, 4, 128, 16, 77, 49408, 128, 2, 4),  # deep-prompt depth coverage
+    # ModifiedResNet backbones (clip.py model table; model.py:94-150): vision_layers = block counts
+    "RN50": ClipArch(1024, 224, (3, 4, 6, 3), 64, None, 77, 49408, 512, 8, 12),
+    "RN101": ClipArch(512, 224, (3, 4, 23, 3), 64, None, 77, 49408, 512, 8, 12),
+    # Small ResNets for parity: full channel widths (64 .. 2048), one block per layer, small maps
+    # (resolution 96: 24 / 12 / 6 / 3) and the tiny text tower.
+    "RN-tiny": ClipArch(128, 64, (1, 1, 1, 1), 64, None, 77, 49408, 128, 2, 2),
+    "RN-tiny-96": ClipArch(128, 96, (2, 1, 1, 1), 64, None, 77, 49408, 128, 2, 2),
 }
 
 
-def _param_specs(a: ClipArch):
-    """(key, shape, kind, std) in a FIXED order; kind in {w, b, lnw, lnb, const}."""
+def _blocks(prefix, width, layers):
+    out = []
+    proj_std = (width ** -0.5) * ((2 * layers) ** -0.5)  # model.py:579-581
+    attn_std = width ** -0.5
+    fc_std = (2 * width) ** -0.5
+    for i in range(layers):
+        p = f"{prefix}.resblocks.{i}."
+        out += [
+            (p + "attn.in_proj_weight", (3 * width, width), "w", attn_std),
+            (p + "attn.in_proj_bias", (3 * width,), "b", 0.0),
+            (p + "attn.out_proj.weight", (width, width), "w", proj_std),
+            (p + "attn.out_proj.bias", (width,), "b", 0.0),
+            (p + "ln_1.weight", (width,), "lnw", 0.0),
+            (p + "ln_1.bias", (width,), "lnb", 0.0),
+            (p + "mlp.c_fc.weight", (4 * width, width), "w", fc_std),
+            (p + "mlp.c_fc.bias", (4 * width,), "b", 0.0),
+            (p + "mlp.c_proj.weight", (width, 4 * width), "w", proj_std),
+            (p + "mlp.c_proj.bias", (width,), "b", 0.0),
+            (p + "ln_2.weight", (width,), "lnw", 0.0),
+            (p + "ln_2.bias", (width,), "lnb", 0.0),
+        ]
+    return out
+
+
+def _text_specs(a: ClipArch):
+    W, E = a.transformer_width, a.embed_dim
+    specs = [
+        ("token_embedding.weight", (a.vocab_size, W), "w", 0.02),   # model.py:564
+        ("positional_embedding", (a.context_length, W), "w", 0.01),  # model.py:565
+    ]
+    specs += _blocks("transformer", W, a.transformer_layers)
+    specs += [
+        ("ln_final.weight", (W,), "lnw", 0.0),
+        ("ln_final.bias", (W,), "lnb", 0.0),
+        ("text_projection", (W, E), "w", W ** -0.5),  # model.py:589-590
+    ]
+    return specs
+
+
+def _resnet_specs(a: ClipArch):
+    """ModifiedResNet keys (model.py:94-150) in a FIXED order. Convolutions feeding a ReLU draw
+    std sqrt(2 / fan_in); a block's conv3 and downsample draw fan_in^-0.5 / 2 and fan_in^-0.5, and
+    BatchNorm is near the identity (weight 1 + N(0, 0.05), bias N(0, 0.02), running_mean N(0, 0.1),
+    running_var U[0.5, 1.5)), so activations stay O(1) through all 16 or 33 blocks."""
+    w = a.vision_width
     specs = []
-    D, W, E = a.vision_width, a.transformer_width, a.embed_dim
+
+    def conv(key, cout, cin, k, std):
+        specs.append((key + ".weight", (cout, cin, k, k), "w", std))
+
+    def bn(key, c):
+        specs.extend([(key + ".weight", (c,), "lnw", 0.0), (key + ".bias", (c,), "lnb", 0.0),
+                      (key + ".running_mean", (c,), "w", 0.1), (key + ".running_var", (c,), "var", 0.0),
+                      (key + ".num_batches_tracked", (), "count", 0.0)])
+
+    for i, (cout, cin) in enumerate(((w // 2, 3), (w // 2, w // 2), (w, w // 2)), 1):
+        conv(f"visual.conv{i}", cout, cin, 3, (2.0 / (9 * cin)) ** 0.5)
+        bn(f"visual.bn{i}", cout)
+    inpl = w
+    for l, n in enumerate(a.vision_layers):
+        planes = w << l
+        for i in range(n):
+            p = f"visual.layer{l + 1}.{i}."
+            conv(p + "conv1", planes, inpl, 1, (2.0 / inpl) ** 0.5)
+            bn(p + "bn1", planes)
+            conv(p + "conv2", planes, planes, 3, (2.0 / (9 * planes)) ** 0.5)
+            bn(p + "bn2", planes)
+            conv(p + "conv3", planes * 4, planes, 1, 0.5 * planes ** -0.5)
+            bn(p + "bn3", planes * 4)
+            if i == 0:  # stride > 1 or inplanes != 4 * planes: every layer's first block
+                conv(p + "downsample.0", planes * 4, inpl, 1, inpl ** -0.5)
+                bn(p + "downsample.1", planes * 4)
+            inpl = planes * 4
+    C, S = inpl, a.image_resolution // 32
+    std = C ** -0.5  # model.py:567-572
+    specs.append(("visual.attnpool.positional_embedding", (S * S + 1, C), "w", std))
+    for name, out in (("q_proj", C), ("k_proj", C), ("v_proj", C), ("c_proj", a.embed_dim)):
+        specs += [(f"visual.attnpool.{name}.weight", (out, C), "w", std), (f"visual.attnpool.{name}.bias", (out,), "b", 0.0)]
+    return specs
+
+
+def _param_specs(a: ClipArch):
+    """(key, shape, kind, std) in a FIXED order; kind in {w, b, lnw, lnb, var, count}."""
+    if a.is_resnet:
+        return _resnet_specs(a) + _text_specs(a)
+    specs = []
+    D, E = a.vision_width, a.embed_dim
     vscale = D ** -0.5  # model.py:386-391
     specs += [
         ("visual.class_embedding", (D,), "w", vscale),
@@ -82,44 +176,12 @@ def _param_specs(a: ClipArch):
         ("visual.ln_pre.weight", (D,), "lnw", 0.0),
         ("visual.ln_pre.bias", (D,), "lnb", 0.0),
     ]
-
-    def blocks(prefix, width, layers):
-        out = []
-        proj_std = (width ** -0.5) * ((2 * layers) ** -0.5)  # model.py:579-581
-        attn_std = width ** -0.5
-        fc_std = (2 * width) ** -0.5
-        for i in range(layers):
-            p = f"{prefix}.resblocks.{i}."
-            out += [
-                (p + "attn.in_proj_weight", (3 * width, width), "w", attn_std),
-                (p + "attn.in_proj_bias", (3 * width,), "b", 0.0),
-                (p + "attn.out_proj.weight", (width, width), "w", proj_std),
-                (p + "attn.out_proj.bias", (width,), "b", 0.0),
-                (p + "ln_1.weight", (width,), "lnw", 0.0),
-                (p + "ln_1.bias", (width,), "lnb", 0.0),
-                (p + "mlp.c_fc.weight", (4 * width, width), "w", fc_std),
-                (p + "mlp.c_fc.bias", (4 * width,), "b", 0.0),
-                (p + "mlp.c_proj.weight", (width, 4 * width), "w", proj_std),
-                (p + "mlp.c_proj.bias", (width,), "b", 0.0),
-                (p + "ln_2.weight", (width,), "lnw", 0.0),
-                (p + "ln_2.bias", (width,), "lnb", 0.0),
-            ]
-        return out
-
-    specs += blocks("visual.transformer", D, a.vision_layers)
+    specs += _blocks("visual.transformer", D, a.vision_layers)
     specs += [
         ("visual.ln_post.weight", (D,), "lnw", 0.0),
         ("visual.ln_post.bias", (D,), "lnb", 0.0),
-        ("token_embedding.weight", (a.vocab_size, W), "w", 0.02),   # model.py:564
-        ("positional_embedding", (a.context_length, W), "w", 0.01),  # model.py:565
     ]
-    specs += blocks("transformer", W, a.transformer_layers)
-    specs += [
-        ("ln_final.weight", (W,), "lnw", 0.0),
-        ("ln_final.bias", (W,), "lnb", 0.0),
-        ("text_projection", (W, E), "w", W ** -0.5),  # model.py:589-590
-    ]
-    return specs
+    return specs + _text_specs(a)
 
 
 def make_state_dict(arch: str | ClipArch, seed: int = 0, logit_scale: float = float(np.log(100.0)),
@@ -132,6 +194,13 @@ def make_state_dict(arch: str | ClipArch, seed: int = 0, logit_scale: float = fl
     rs = np.random.RandomState(seed)
     sd = {}
     for key, shape, kind, std in _param_specs(a):
+        if kind == "count":  # BatchNorm's num_batches_tracked
+            sd[key] = np.asarray(0, dtype=np.int64)
+            continue
+        if kind == "var":  # BatchNorm's running_var in [0.5, 1.5)
+            v = 0.5 + rs.random_sample(size=shape)
+            sd[key] = np.ascontiguousarray(v.astype(np.float16) if fp16_values else v, dtype=np.float32)
+            continue
         z = rs.standard_normal(size=shape)
         if kind == "w":
             v = z * std

@@ -29,21 +29,27 @@ import torch
 
 from .. import dist
 from ..clip import synth
-from ..clip.model import build_model
+from ..clip.model import arch_from_state_dict, build_model, require_vit
 from ..clip.weights import load_state_dict
 from . import checkpoint as ckpt
 from .metrics import Classification
 
 
-def load_clip(cfg, prec, device, text_grad=True, vision_grad=False):
+def load_clip(cfg, prec, device, text_grad=True, vision_grad=False, vit_only=None):
     """Replacement for load_clip_to_cpu (coop.py:165-184): the CLIP weights file at
     MODEL.WEIGHTS_PATH (OpenAI TorchScript archive, torch.save state dict, .npz or
     .safetensors; clip/weights.py), otherwise the seeded synthetic CLIP of
     MODEL.BACKBONE.NAME (no network on this path). text_grad=False packs no backward
-    weights (forward-only text encoder, e.g. zero-shot)."""
+    weights (forward-only text encoder, e.g. zero-shot). vit_only: the name of a trainer that
+    needs a ViT image encoder -- a ModifiedResNet backbone raises ValueError (require_vit)."""
     path = cfg.MODEL.get("WEIGHTS_PATH", "")
+    name = cfg.MODEL.BACKBONE.NAME
+    if vit_only and not path and name in synth.ARCHS:
+        require_vit(vit_only, name, synth.ARCHS[name])  # before the weights are drawn
     sd = load_state_dict(path) if path else synth.make_state_dict(
-        cfg.MODEL.BACKBONE.NAME, seed=0, fp16_values=bool(cfg.MODEL.get("SYNTH_FP16", False)))
+        name, seed=0, fp16_values=bool(cfg.MODEL.get("SYNTH_FP16", False)))
+    if vit_only:
+        require_vit(vit_only, name, arch_from_state_dict(sd))
     return build_model(sd, prec=prec, device=device, text_grad=text_grad, vision_grad=vision_grad)
 
 

@@ -808,3 +808,72 @@ def encoder_set_lora(handle, rank, proj_mask=0, layer_mask=0, scale=0.0, A=None,
     """clipk_encoder_set_lora on an encoder handle (rank 0 clears)."""
     N.call("clipk_encoder_set_lora", handle, int(rank), int(proj_mask), int(layer_mask), float(scale), _p(A), _p(B),
            _p(dA), _p(dB))
+
+
+# ---------------------------------------------------------------- ModifiedResNet kernels
+def conv2d_nhwc(x, w, scale=None, shift=None, res=None, relu=False, ksize=1, out_f32=False, out=None):
+    """clipk_conv2d_nhwc: x [B,H,W,Cin], w [Cout, ksize^2 Cin] (k = tap * Cin + c), both x's dtype
+    -> out [B,H,W,Cout] = relu?(acc * scale + shift (+ res)) rounded once (out_f32: stored as fp32).
+    Stride 1, pad ksize // 2. The library checks the shape constraints (CLIPK_EINVAL)."""
+    _need(x, "x")
+    _need(w, "w", x.dtype)
+    B, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    if w.shape[1] != ksize * ksize * Cin:
+        raise N.ClipkError(f"conv2d_nhwc: w must be [Cout, {ksize * ksize * Cin}], got {tuple(w.shape)}")
+    for t, name in ((scale, "scale"), (shift, "shift")):
+        if t is not None and _need(t, name, torch.float32).numel() != Cout:
+            raise N.ClipkError(f"conv2d_nhwc: {name} must have Cout elements")
+    odt = torch.float32 if out_f32 else x.dtype
+    if out is None:
+        out = torch.empty(B, H, W, Cout, dtype=odt, device=x.device)
+    elif _need(out, "out", odt).numel() != B * H * W * Cout:
+        raise N.ClipkError("conv2d_nhwc: out must hold B*H*W*Cout elements")
+    if res is not None and _need(res, "res", x.dtype).numel() != B * H * W * Cout:
+        raise N.ClipkError("conv2d_nhwc: res must have out's shape")
+    flags = (N.CONV_RES if res is not None else 0) | (N.CONV_RELU if relu else 0) | (N.CONV_OUT_F32 if out_f32 else 0)
+    N.call("clipk_conv2d_nhwc", DT[x.dtype], flags, B, H, W, Cin, Cout, ksize, _p(x), _p(w), _p(scale), _p(shift),
+           _p(res), _p(out), _stream())
+    return out
+
+
+def im2col_3x3s2(img, out_dtype):
+    """clipk_im2col_3x3s2: img fp32 [B,3,R,R] -> [B (R/2)^2, 32] rows of the stem's 3x3 / stride-2
+    taps, k = (ky * 3 + kx) * 3 + c, zero padded from 27."""
+    _need(img, "img", torch.float32)
+    B, _, R, _ = img.shape
+    out = torch.empty(B * (R // 2) ** 2, 32, dtype=out_dtype, device=img.device)
+    N.call("clipk_im2col_3x3s2", DT[out_dtype], B, R, _p(img), _p(out), _stream())
+    return out
+
+
+def avgpool2_nhwc(x, out=None):
+    """clipk_avgpool2_nhwc: AvgPool2d(2) of x [B,H,W,C] (fp32 sum, one rounding)."""
+    _need(x, "x")
+    B, H, W, C = x.shape
+    if out is None:
+        out = torch.empty(B, H // 2, W // 2, C, dtype=x.dtype, device=x.device)
+    else:
+        _need(out, "out", x.dtype)
+    N.call("clipk_avgpool2_nhwc", DT[x.dtype], B, H, W, C, _p(x), _p(out), _stream())
+    return out
+
+
+def attnpool(x, pos, q_w, q_b, kv_w, kv_b, c_w, c_b, heads):
+    """clipk_attnpool: x [B, HW, C] -> fp32 [B, E] (AttentionPool2d: the mean token is the only
+    query). kv_w [2C, C] is k_proj.weight over v_proj.weight; weights in x's dtype, pos / biases fp32."""
+    _need(x, "x")
+    B, HW, C = x.shape
+    E = c_w.shape[0]
+    for t, name in ((q_w, "q_w"), (kv_w, "kv_w"), (c_w, "c_w")):
+        _need(t, name, x.dtype)
+    for t, name in ((pos, "pos"), (q_b, "q_b"), (kv_b, "kv_b"), (c_b, "c_b")):
+        _need(t, name, torch.float32)
+    if pos.shape != (HW + 1, C) or q_w.shape != (C, C) or kv_w.shape != (2 * C, C) or c_w.shape != (E, C):
+        raise N.ClipkError("attnpool: pos [HW+1, C], q_w [C, C], kv_w [2C, C], c_w [E, C] expected")
+    feat = torch.empty(B, E, dtype=torch.float32, device=x.device)
+    wsb = N.load().clipk_attnpool_ws_bytes(DT[x.dtype], B, HW, C)
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=x.device)
+    N.call("clipk_attnpool", DT[x.dtype], B, HW, C, heads, E, _p(x), _p(pos), _p(q_w), _p(q_b), _p(kv_w), _p(kv_b),
+           _p(c_w), _p(c_b), _p(feat), _p(ws), ws.numel(), _stream())
+    return feat

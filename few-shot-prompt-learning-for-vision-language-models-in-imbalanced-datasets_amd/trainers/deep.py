@@ -240,7 +240,8 @@ class _DeepTrainer(TrainerX):
     def build_model(self):
         cfg = self.cfg
         classnames = self.dm.dataset.classnames
-        clip_model = load_clip(cfg, self.sec.PREC, self.device, vision_grad=self._vision_trains())
+        clip_model = load_clip(cfg, self.sec.PREC, self.device, vision_grad=self._vision_trains(),
+                               vit_only=type(self).__name__)
         print(f"Building custom CLIP ({self.SEC})")
         self.model = self._make_model(classnames, clip_model).to(self.device)
         # the reference's selection: prompt_learner.* and every *VPT* (independentVL.py:385-391)

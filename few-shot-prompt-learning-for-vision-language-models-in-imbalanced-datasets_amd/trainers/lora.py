@@ -218,12 +218,15 @@ class LoRA(TrainerX):
         classnames = self.dm.dataset.classnames
         from ..clip import synth
         from ..clip.weights import load_state_dict
-        from ..clip.model import arch_from_state_dict, build_model
+        from ..clip.model import arch_from_state_dict, build_model, require_vit
         path = cfg.MODEL.get("WEIGHTS_PATH", "")
         print(f"Loading CLIP (backbone: {cfg.MODEL.BACKBONE.NAME})")
+        if not path and cfg.MODEL.BACKBONE.NAME in synth.ARCHS:
+            require_vit("LoRA", cfg.MODEL.BACKBONE.NAME, synth.ARCHS[cfg.MODEL.BACKBONE.NAME])
         sd = load_state_dict(path) if path else synth.make_state_dict(
             cfg.MODEL.BACKBONE.NAME, seed=0, fp16_values=bool(cfg.MODEL.get("SYNTH_FP16", False)))
         arch = arch_from_state_dict(sd)
+        require_vit("LoRA", cfg.MODEL.BACKBONE.NAME, arch)
         text_on, vision_on = sec.ENCODER in ("both", "text"), sec.ENCODER in ("both", "vision")
         tspec, vspec = lora_spec(sec, arch.transformer_layers), lora_spec(sec, arch.vision_layers)
         clip_model = build_model(sd, prec=sec.PREC, device=self.device, text_grad=text_on, vision_grad=vision_on,

@@ -42,6 +42,11 @@
  *                         amsgrad, adamw)
  *   clipk_text_*          TextEncoder.forward + its input-grad backward (coop.py:195-205)
  *   clipk_vit_forward     VisionTransformer.forward (model.py:401-431), frozen, fwd only
+ *   clipk_conv2d_nhwc     nn.Conv2d (1x1, 3x3 pad 1) + eval BatchNorm2d + residual + ReLU of
+ *                         Bottleneck / the stem (model.py:10-56, 94-150)
+ *   clipk_avgpool2_nhwc   nn.AvgPool2d(2) (model.py:27, 34-40, 115)
+ *   clipk_attnpool        AttentionPool2d (model.py:58-91)
+ *   clipk_resnet_forward  ModifiedResNet.forward (model.py:135-150), frozen, fwd only
  */
 #ifndef CLIPK_H
 #define CLIPK_H
@@ -816,6 +821,58 @@ int clipk_vision_create(int width, int layers, int heads, int embed, int res, in
 size_t clipk_vit_ws_bytes(const clipk_encoder* enc, int B);
 int clipk_vit_forward(const clipk_encoder* enc, int B, const float* img, float* feat, void* ws,
                       size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- ModifiedResNet (RN50 / RN101)
+ * CLIP's ResNet image tower (PromptSRC/clip/model.py:10-150), frozen and forward-only. Activations
+ * are NHWC in the act dtype (CLIPK_F32 / CLIPK_F16 / CLIPK_BF16), every pointer 16-B aligned.
+ * Every violation below returns CLIPK_EINVAL before any launch. No atomics, no split-K: two
+ * calls agree bitwise. */
+enum { CLIPK_CONV_RES = 1, CLIPK_CONV_RELU = 2, CLIPK_CONV_OUT_F32 = 4 };
+/* Implicit-GEMM convolution on the MFMA (16-bit: mfma_f32_16x16x32, fp32: mfma_f32_16x16x4f32;
+ * fp32 accumulation), stride 1, pad ksize / 2, ksize 1 or 3, Cin % 32 == 0, Cout % 32 == 0, any
+ * M = B H W. x [B,H,W,Cin], w [Cout, ksize^2 Cin] (k = tap * Cin + c, tap = ky * ksize + kx), both
+ * dtype; out [B,H,W,Cout] = max(acc * scale[n] + shift[n] + res, 0) in fp32, rounded once (scale /
+ * shift fp32 [Cout], the frozen BatchNorm's; null: 1 / 0). CLIPK_CONV_RES adds res (dtype, the
+ * shape of out), CLIPK_CONV_RELU clamps, CLIPK_CONV_OUT_F32 stores out as fp32. A tap outside the
+ * image contributes zero and is never read: its index is clamped into the image and zero is
+ * selected. */
+int clipk_conv2d_nhwc(int dtype, int flags, int B, int H, int W, int Cin, int Cout, int ksize,
+                      const void* x, const void* w, const float* scale, const float* shift,
+                      const void* res, void* out, void* stream);
+/* The stem's conv1 (3 -> Cout, 3x3, stride 2, pad 1) as a gather for the 1x1 path: img fp32
+ * [B,3,R,R] -> out [B (R/2)^2, 32] (out_dtype), k = (ky * 3 + kx) * 3 + c, zero for k >= 27. R even. */
+int clipk_im2col_3x3s2(int out_dtype, int B, int res, const float* img, void* out, void* stream);
+/* AvgPool2d(2) on NHWC: the four values summed in fp32, times 0.25, rounded once. H, W even,
+ * C % 8 == 0. */
+int clipk_avgpool2_nhwc(int dtype, int B, int H, int W, int C, const void* x, void* out, void* stream);
+/* AttentionPool2d: x [B, HW, C] (dtype) -> feat fp32 [B, E]. The mean token (fp32 sum) is
+ * prepended, pos fp32 [HW + 1, C] added, and one multi-head attention runs with the mean token as
+ * the only query: q = q_w tok0 + q_b scaled by 64^-0.5, k | v = kv_w tok + kv_b for every token
+ * (kv_w [2C, C]: k_proj over v_proj), fp32 softmax, feat = c_w o + c_b. Weights [out, in] in dtype,
+ * biases fp32. C == 64 heads, HW + 1 <= 256, E % 32 == 0; ws 16-B aligned, at least
+ * clipk_attnpool_ws_bytes (else CLIPK_EWORKSPACE). */
+size_t clipk_attnpool_ws_bytes(int dtype, int B, int HW, int C);
+int clipk_attnpool(int dtype, int B, int HW, int C, int heads, int E, const void* x, const float* pos,
+                   const void* q_w, const float* q_b, const void* kv_w, const float* kv_b,
+                   const void* c_w, const float* c_b, float* feat, void* ws, size_t ws_bytes,
+                   void* stream);
+/* The whole tower: img fp32 [B,3,R,R] -> feat fp32 [B, embed]. width = layer1's planes (64),
+ * blocks = the four block counts, res % 32 == 0. Weights are not owned. ptrs, in order:
+ *   stem: conv1 w [width/2, 32] (clipk_im2col_3x3s2's k order), scale, shift; conv2 w, scale,
+ *         shift; conv3 w, scale, shift;
+ *   per block: conv1 w, scale, shift, conv2 w, scale, shift, conv3 w, scale, shift, downsample w,
+ *         scale, shift (three nulls where the block has none);
+ *   attnpool: pos, q_w, q_b, kv_w, kv_b, c_w, c_b
+ * -- n_ptrs = 9 + 12 * (number of blocks) + 7. Convolution weights in act_dtype, repacked to
+ * clipk_conv2d_nhwc's [Cout, ksize^2 Cin]; scale = bn.weight / sqrt(running_var + 1e-5), shift =
+ * bn.bias - running_mean * scale, fp32. */
+typedef struct clipk_resnet clipk_resnet;
+int clipk_resnet_create(int width, const int* blocks, int embed, int res, int act_dtype,
+                        const void* const* ptrs, int n_ptrs, clipk_resnet** out);
+void clipk_resnet_destroy(clipk_resnet* h);
+size_t clipk_resnet_ws_bytes(const clipk_resnet* h, int B);
+int clipk_resnet_forward(const clipk_resnet* h, int B, const float* img, float* feat, void* ws,
+                         size_t ws_bytes, void* stream);
 
 /* Per-kernel-class timing with hipEvents on the launch stream (bench.py roofline). */
 enum { CLIPK_PROF_NONE = 0, CLIPK_PROF_GEMM_FC = 1, CLIPK_PROF_GEMM_ALL = 2, CLIPK_PROF_ATTN = 3,
