@@ -143,6 +143,16 @@ __device__ __forceinline__ float quick_gelu_grad(float x) {
   return s * fmaf(1.702f * x, 1.0f - s, 1.0f);  // s + 1.702 x s (1 - s)
 }
 
+// MultiClassFocalLoss row terms (coop.py:145-163) from the row's ce, p = exp(-ce) (the caller's
+// exp) and a = alpha_y: the loss l = a (1-p)^g ce and the weight wgt of d ce / d logits in its
+// gradient, a ((1-p)^g + g p (1-p)^(g-1) ce). A row whose p rounds to 1 (om == 0) takes the
+// second term's limit 0: for g < 1 the expression itself is inf * 0 = NaN there.
+__device__ __forceinline__ void focal_terms(float ce, float p, float a, float gamma, float& l, float& wgt) {
+  const float om = 1.f - p;
+  l = a * powf(om, gamma) * ce;
+  wgt = a * (powf(om, gamma) + (gamma != 0.f && om != 0.f ? gamma * p * powf(om, gamma - 1.f) * ce : 0.f));
+}
+
 // The lo parts of a split (hi = fp16(x), lo = fp16(x - hi)) of 4 fp32 values whose hi parts are
 // the fp16 pairs h01 = (x0, x1), h23 = (x2, x3): v_fma_mix forms x - hi exactly in fp32 and
 // rounds once, bitwise (_Float16)(x - (float)hi), in 4 instructions instead of cvt + sub + cvt

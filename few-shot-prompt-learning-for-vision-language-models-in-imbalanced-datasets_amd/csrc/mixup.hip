@@ -87,11 +87,7 @@ __device__ __forceinline__ void target_terms(const float* __restrict__ z, int C,
   l = ce;
   wgt = 1.f;
   if (focal) {
-    const float p = __expf(-ce);
-    const float a = alpha ? alpha[y] : 1.f;
-    const float om = 1.f - p;
-    l = a * powf(om, gamma) * ce;
-    wgt = a * (powf(om, gamma) + (gamma != 0.f ? gamma * p * powf(om, gamma - 1.f) * ce : 0.f));
+    focal_terms(ce, __expf(-ce), alpha ? alpha[y] : 1.f, gamma, l, wgt);
   }
 }
 
@@ -206,6 +202,7 @@ extern "C" int clipk_ce_loss_mix(int B, int C, const float* logits, const int64_
                                  int reduction, float* row_loss, float* loss, float* dlogits, void* stream) {
   if (!logits || !y_a || !y_b || !row_loss || !loss) return CLIPK_EINVAL;
   if (reduction != 1 && reduction != 2) return CLIPK_EINVAL;
+  if (focal && !(gamma >= 0.f)) return CLIPK_EINVAL;
   if (B <= 0 || C <= 0) return CLIPK_ESHAPE;
   const int mean = reduction == 1 ? 1 : 0;
   if (C <= 64 * ROWQ)

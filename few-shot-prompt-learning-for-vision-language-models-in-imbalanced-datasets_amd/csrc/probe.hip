@@ -174,11 +174,7 @@ __device__ __forceinline__ float row_wave(int C, int lane, const float* __restri
     l = ce;
     wgt = 1.f;
     if (focal) {
-      const float p = expf(-ce);
-      const float a = alpha ? alpha[y] : 1.f;
-      const float om = 1.f - p;
-      l = a * powf(om, gamma) * ce;
-      wgt = a * (powf(om, gamma) + (gamma != 0.f ? gamma * p * powf(om, gamma - 1.f) * ce : 0.f));
+      focal_terms(ce, expf(-ce), alpha ? alpha[y] : 1.f, gamma, l, wgt);
     }
   }
   if (g) {

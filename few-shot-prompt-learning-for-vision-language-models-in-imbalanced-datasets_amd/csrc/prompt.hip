@@ -320,11 +320,7 @@ __global__ __launch_bounds__(64) void ce_loss_kernel(int B, int C, const float* 
   const float ce = lse - z[y];
   float wgt = 1.f, loss = ce;
   if (focal) {
-    const float p = __expf(-ce);
-    const float a = alpha ? alpha[y] : 1.f;
-    const float om = 1.f - p;
-    loss = a * powf(om, gamma) * ce;
-    wgt = a * (powf(om, gamma) + (gamma != 0.f ? gamma * p * powf(om, gamma - 1.f) * ce : 0.f));
+    focal_terms(ce, __expf(-ce), alpha ? alpha[y] : 1.f, gamma, loss, wgt);
   }
   if (lane == 0 && row_loss) row_loss[b] = loss;
   if (dlogits) {
@@ -358,11 +354,7 @@ __global__ __launch_bounds__(256) void ce_loss_reduce_kernel(int B, int C, const
     const float ce = lse - z[y];
     float wgt = 1.f, l = ce;
     if (focal) {
-      const float p = __expf(-ce);
-      const float a = alpha ? alpha[y] : 1.f;
-      const float om = 1.f - p;
-      l = a * powf(om, gamma) * ce;
-      wgt = a * (powf(om, gamma) + (gamma != 0.f ? gamma * p * powf(om, gamma - 1.f) * ce : 0.f));
+      focal_terms(ce, __expf(-ce), alpha ? alpha[y] : 1.f, gamma, l, wgt);
     }
     if (lane == 0) row_loss[b] = l;
     if (dlogits)
@@ -796,6 +788,7 @@ extern "C" int clipk_ce_loss(int B, int C, const float* logits, const int64_t* l
                              const float* alpha, float gamma, int focal, float grad_scale,
                              float* row_loss, float* dlogits, void* stream) {
   if (!logits || !labels) return CLIPK_EINVAL;
+  if (focal && !(gamma >= 0.f)) return CLIPK_EINVAL;
   if (B < 0 || C <= 0) return CLIPK_ESHAPE;
   if (B == 0) return CLIPK_OK;
   hipLaunchKernelGGL(ce_loss_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, C, logits, labels,
@@ -848,6 +841,7 @@ extern "C" int clipk_ce_loss_reduce(int B, int C, const float* logits, const int
                                     float* loss, float* dlogits, void* stream) {
   if (!logits || !labels || !row_loss || !loss) return CLIPK_EINVAL;
   if (reduction != 1 && reduction != 2) return CLIPK_EINVAL;
+  if (focal && !(gamma >= 0.f)) return CLIPK_EINVAL;
   if (B <= 0 || C <= 0) return CLIPK_ESHAPE;
   hipLaunchKernelGGL(ce_loss_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, B, C, logits, labels, alpha,
                      gamma, focal, grad_scale, reduction == 1 ? 1 : 0, row_loss, loss, dlogits);

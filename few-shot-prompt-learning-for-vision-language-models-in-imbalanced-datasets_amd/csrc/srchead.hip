@@ -315,11 +315,7 @@ __global__ __launch_bounds__(256) void rows_kernel(int B, int C, int splits, flo
     l = ce;
     wgt = 1.f;
     if (focal) {
-      const float p = expf(-ce);
-      const float a = alpha ? alpha[y] : 1.f;
-      const float om = 1.f - p;
-      l = a * powf(om, gamma) * ce;
-      wgt = a * (powf(om, gamma) + (gamma != 0.f ? gamma * p * powf(om, gamma - 1.f) * ce : 0.f));
+      focal_terms(ce, expf(-ce), alpha ? alpha[y] : 1.f, gamma, l, wgt);
     }
   }
   const float cw = wgt * inv_b;

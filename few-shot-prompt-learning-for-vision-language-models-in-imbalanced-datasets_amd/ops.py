@@ -300,6 +300,11 @@ def im2col(img, patch, Kp, out_dtype):
 
 
 def prompt_assemble(B, C, L, src_map, emb, ctx, ctx_sb, ctx_sc, bias, pos):
+    _need(src_map, "src_map", torch.int32)
+    for t, name in ((emb, "emb"), (ctx, "ctx"), (pos, "pos")):
+        _need(t, name, torch.float32)
+    if bias is not None:
+        _need(bias, "bias", torch.float32)
     W = emb.shape[-1]
     x0 = torch.empty(B * C * L, W, device=emb.device, dtype=torch.float32)
     N.call("clipk_prompt_assemble", B, C, L, W, _p(src_map), _p(emb), _p(ctx), ctx_sb, ctx_sc, _p(bias),
@@ -363,6 +368,8 @@ def attention_prefix_bwd(qkv, o, dout, lse, G, P, R, tiles, row_first, heads, gr
 
 
 def ctx_grad(B, C, L, W, n_ctx, csc, ctx_pos, dx0):
+    _need(ctx_pos, "ctx_pos", torch.int32)
+    _need(dx0, "dx0", torch.float32)
     outs = (B * C if csc else B) * n_ctx
     d = torch.empty(outs, W, device=dx0.device, dtype=torch.float32)
     N.call("clipk_ctx_grad", B, C, L, W, n_ctx, int(csc), _p(ctx_pos), _p(dx0), _p(d), _stream())
@@ -370,6 +377,8 @@ def ctx_grad(B, C, L, W, n_ctx, csc, ctx_pos, dx0):
 
 
 def cosine_logits(imf, txt, scale, per_image, C):
+    _need(imf, "imf", torch.float32)
+    _need(txt, "txt", torch.float32)
     B, E = imf.shape
     logits = torch.empty(B, C, device=imf.device)
     inv_t = torch.empty(txt.shape[0], device=imf.device)
@@ -380,11 +389,13 @@ def cosine_logits(imf, txt, scale, per_image, C):
 
 
 def cosine_logits_bwd(imf, txt, inv_t, inv_i, dlogits, scale, per_image):
+    for t, name in ((imf, "imf"), (txt, "txt"), (inv_t, "inv_t"), (inv_i, "inv_i"), (dlogits, "dlogits")):
+        _need(t, name, torch.float32)
     B, C = dlogits.shape
     E = imf.shape[1]
     dtxt = torch.empty_like(txt)
     N.call("clipk_cosine_logits_bwd", B, C, E, int(per_image), float(scale), _p(imf), _p(txt),
-           _p(inv_t), _p(inv_i), _p(dlogits.contiguous()), _p(dtxt), _stream())
+           _p(inv_t), _p(inv_i), _p(dlogits), _p(dtxt), _stream())
     return dtxt
 
 
@@ -400,6 +411,8 @@ def ce_loss(logits, labels, alpha=None, gamma=2.0, focal=False, grad=True, grad_
         _need(alpha, "alpha", torch.float32)
         if alpha.numel() < C:
             raise N.ClipkError(f"alpha must hold {C} class weights, got {alpha.numel()}")
+    if focal and not gamma >= 0:
+        raise N.ClipkError(f"focal needs gamma >= 0, got {gamma}")
     row = torch.empty(B, device=logits.device)
     dl = torch.empty_like(logits) if grad else None
     N.call("clipk_ce_loss", B, C, _p(logits), _p(labels), _p(alpha), float(gamma), int(focal),
@@ -409,6 +422,8 @@ def ce_loss(logits, labels, alpha=None, gamma=2.0, focal=False, grad=True, grad_
 
 def meta_net(x, w1, b1, w2, b2, normalize=False):
     """(h, y); normalize: the Meta-Net on x / |x| (clipk_meta_net_fwd_norm) -> (xn, h, y)."""
+    for t, name in ((x, "x"), (w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2")):
+        _need(t, name, torch.float32)
     B, V = x.shape
     Hd, Wd = w1.shape[0], w2.shape[0]
     h = torch.empty(B, Hd, device=x.device)
@@ -435,6 +450,8 @@ def ce_loss_reduce(logits, labels, alpha=None, gamma=2.0, focal=False, grad=True
         _need(alpha, "alpha", torch.float32)
         if alpha.numel() < C:
             raise N.ClipkError(f"alpha must hold {C} class weights, got {alpha.numel()}")
+    if focal and not gamma >= 0:
+        raise N.ClipkError(f"focal needs gamma >= 0, got {gamma}")
     red = {"mean": 1, "sum": 2}[reduction]
     row = torch.empty(B, device=logits.device)
     loss = torch.empty((), device=logits.device)
@@ -459,6 +476,8 @@ def ce_loss_mix(logits, y_a, y_b, lam, alpha=None, gamma=2.0, focal=False, grad=
         _need(alpha, "alpha", torch.float32)
         if alpha.numel() < C:
             raise N.ClipkError(f"alpha must hold {C} class weights, got {alpha.numel()}")
+    if focal and not gamma >= 0:
+        raise N.ClipkError(f"focal needs gamma >= 0, got {gamma}")
     red = {"mean": 1, "sum": 2}[reduction]
     row = torch.empty(2 * B, device=logits.device)
     loss = torch.empty((), device=logits.device)
@@ -639,18 +658,24 @@ def status_take(flags, host_word):
 
 
 def meta_net_bwd(x, h, w2, dy, V, Hd, Wd):
+    for t, name in ((x, "x"), (h, "h"), (w2, "w2"), (dy, "dy")):
+        _need(t, name, torch.float32)
     B = x.shape[0]
     dw1 = torch.empty(Hd, V, device=x.device)
     db1 = torch.empty(Hd, device=x.device)
     dw2 = torch.empty(Wd, Hd, device=x.device)
     db2 = torch.empty(Wd, device=x.device)
     dh = torch.empty(B, Hd, device=x.device)
-    N.call("clipk_meta_net_bwd", B, V, Hd, Wd, _p(x), _p(h), _p(w2), _p(dy.contiguous()), _p(dw1),
+    N.call("clipk_meta_net_bwd", B, V, Hd, Wd, _p(x), _p(h), _p(w2), _p(dy), _p(dw1),
            _p(db1), _p(dw2), _p(db2), _p(dh), _stream())
     return dw1, db1, dw2, db2
 
 
 def sgd_step(p, g, buf, lr, momentum, weight_decay, has_buf):
+    for t, name in ((p, "p"), (g, "g"), (buf, "buf")):
+        _need(t, name, torch.float32)
+    if g.numel() != p.numel() or buf.numel() != p.numel():
+        raise N.ClipkError("sgd_step: p, g and buf must have one size")
     N.call("clipk_sgd_step", p.numel(), _p(p), _p(g), _p(buf), float(lr), float(momentum),
            float(weight_decay), int(has_buf), _stream())
 
@@ -714,8 +739,11 @@ def adam_step_multi(ps, gs, ms, vs, vmaxs, steps, parities, lr, beta1, beta2, ep
 
 
 def cast(x, dtype):
+    _need(x, "x", torch.float32)
+    if dtype not in DT:
+        raise N.ClipkError(f"cast: fp32 -> fp32 / fp16 / bf16 only, got {dtype}")
     y = torch.empty(x.shape, device=x.device, dtype=dtype)
-    N.call("clipk_cast", DT[dtype], x.numel(), _p(x.contiguous()), _p(y), _stream())
+    N.call("clipk_cast", DT[dtype], x.numel(), _p(x), _p(y), _stream())
     return y
 
 

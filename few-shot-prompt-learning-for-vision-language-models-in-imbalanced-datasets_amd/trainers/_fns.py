@@ -300,7 +300,7 @@ class MetaNetNormFn(torch.autograd.Function):
             return None, None, None, None, None
         xn, h, w2 = ctx.saved_tensors
         V, Hd, Wd = ctx.dims
-        dw1, db1, dw2, db2 = ops.meta_net_bwd(xn, h, w2.contiguous(), dy, V, Hd, Wd)
+        dw1, db1, dw2, db2 = ops.meta_net_bwd(xn, h, w2.contiguous(), dy.contiguous(), V, Hd, Wd)
         return None, dw1, db1, dw2, db2
 
 
@@ -319,5 +319,5 @@ class MetaNetFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, h, w2 = ctx.saved_tensors
         V, Hd, Wd = ctx.dims
-        dw1, db1, dw2, db2 = ops.meta_net_bwd(x, h, w2.contiguous(), dy, V, Hd, Wd)
+        dw1, db1, dw2, db2 = ops.meta_net_bwd(x, h, w2.contiguous(), dy.contiguous(), V, Hd, Wd)
         return None, dw1, db1, dw2, db2

@@ -447,7 +447,9 @@ int clipk_cosine_logits_bwd(int B, int C, int E, int per_image, float scale, con
                             const float* dlogits, float* dtxt, void* stream);
 
 /* Row-wise CE / focal (gamma) loss with optional per-class alpha; writes per-row loss and
- * dlogits = d(mean loss)/dlogits * grad_scale. */
+ * dlogits = d(mean loss)/dlogits * grad_scale. focal with gamma < 0 (or NaN): CLIPK_EINVAL, here and
+ * in clipk_ce_loss_reduce / clipk_ce_loss_mix. A row whose label probability rounds to 1 has loss and
+ * dlogits exactly 0 for every gamma > 0 (the limit; csrc/common.h focal_terms). */
 int clipk_ce_loss(int B, int C, const float* logits, const int64_t* labels, const float* alpha,
                   float gamma, int focal, float grad_scale, float* row_loss, float* dlogits,
                   void* stream);
