@@ -80,5 +80,36 @@ CLIPK_COLOR_FN void hue_shift(int& r, int& g, int& b, int shift) {
   }
 }
 
+// ---- Gaussian blur (ImageFilter.GaussianBlur: libImaging BoxBlur.c, three box passes per axis) ----
+// One output of a box pass of integer radius r: acc = the 2r + 1 window samples summed, far = the two
+// samples just outside it, ww / fw their 24-bit fixed-point weights ((2r + 1) * ww + 2 * fw <= 2^24,
+// so the sum stays below 255 * 2^24 + 2^23 < 2^32).
+CLIPK_COLOR_FN uint32_t box_px(uint32_t acc, uint32_t far, uint32_t ww, uint32_t fw) {
+  return (acc * ww + far * fw + (1u << 23)) >> 24;
+}
+
+// One box pass over the line p[0], p[stride], ..., p[(n - 1) * stride], in place; edges repeat the
+// edge sample (also when r + 1 >= n). 0 <= r <= 7. The window slides: the samples behind x that the
+// line no longer holds (x - 8 .. x, already overwritten or about to be) ride in `hist`, byte k =
+// in[x - k], and `old` = in[x - 8]; the samples ahead are read from the line, which is still input
+// there. Started on in[0] everywhere, the history is the left edge rule.
+CLIPK_COLOR_FN void box_line(uint8_t* p, int n, int stride, int r, uint32_t ww, uint32_t fw) {
+  const uint32_t first = p[0];
+  uint64_t hist = first * 0x0101010101010101ull;
+  uint32_t old = first;
+  uint32_t acc = (uint32_t)(r + 1) * first;
+  for (int d = 1; d <= r; ++d) acc += p[(size_t)(d < n ? d : n - 1) * stride];
+  for (int x = 0; x < n; ++x) {
+    uint8_t* px = p + (size_t)x * stride;
+    old = (uint32_t)(hist >> 56);
+    hist = (hist << 8) | *px;
+    const int xr = x + r + 1;
+    const uint32_t right = p[(size_t)(xr < n ? xr : n - 1) * stride];
+    const uint32_t left = r < 7 ? (uint32_t)(hist >> (8 * (r + 1))) & 255u : old;
+    *px = (uint8_t)box_px(acc, left + right, ww, fw);
+    acc += right - ((uint32_t)(hist >> (8 * r)) & 255u);  // window of x + 1
+  }
+}
+
 }  // namespace color
 }  // namespace clipk

@@ -3,6 +3,7 @@
 // window, horizontal flip, and torchvision ToTensor + Normalize in fp32.
 // Colour stage (clipk_image_color, below): torchvision ColorJitter / RandomGrayscale on the
 // resampled uint8 pixels, Pillow-exact, one workgroup per image (arithmetic in color_ops.h).
+// clipk_image_color_blur: the same launch followed by Pillow's GaussianBlur on the image.
 //
 // Replaces the Dassl/torchvision PIL transforms (Dassl.pytorch/dassl/data/transforms/
 // transforms.py:206-354: Resize + CenterCrop for test, RandomResizedCrop + flip for train)
@@ -99,6 +100,12 @@ __global__ __launch_bounds__(256) void resample_v_kernel(int B, int S, const lon
 // aligned dword per plane). In-place form (3 * S * S bytes do not fit): the same loop on the
 // caller's uint8 buffer. Groups that are not a whole aligned dword -- the tail of a plane when
 // S * S % 4 != 0, and any group of a misaligned plane in global memory -- move byte by byte.
+// Blur (descriptors of CLIPK_COLORBLUR_DESC ints, r >= 0; uniform over the workgroup): after the
+// program, between two barriers, the lanes give up their pixels and take lines instead -- lane l
+// the row l % S of plane l / S for the three box passes along x (one lane keeps its row, so no
+// barrier between them), a barrier, then the column l % S for the three along y. A pass runs in
+// place (color::box_line: a sliding window, the overwritten inputs in registers), so the image
+// needs no second copy. An image with r = -1 skips all of it: the barriers too.
 constexpr int kColorThreads = 1024;
 constexpr int kColorLdsBytes = 3 * 224 * 224;  // 150,528 B of the CU's 160 KiB; the rest: reduction
 
@@ -134,7 +141,7 @@ __device__ __forceinline__ unsigned long long color_block_sum(unsigned v, unsign
 
 template <bool LDS>
 __global__ __launch_bounds__(kColorThreads) void color_kernel(int S, uint8_t* __restrict__ pix,
-                                                              const int* __restrict__ prog,
+                                                              const int* __restrict__ prog, int desc,
                                                               const float* __restrict__ mean,
                                                               const float* __restrict__ stdv, int out_u8,
                                                               void* __restrict__ out) {
@@ -145,8 +152,9 @@ __global__ __launch_bounds__(kColorThreads) void color_kernel(int S, uint8_t* __
   uint8_t* src = pix + (size_t)b * 3 * n;
   const int P = LDS ? ng * 4 : n;  // plane stride of the working copy
   uint8_t* img = LDS ? reinterpret_cast<uint8_t*>(s_img) : src;
-  const int* pr = prog + (size_t)b * CLIPK_COLOR_DESC;
+  const int* pr = prog + (size_t)b * desc;  // desc ints per image: CLIPK_COLOR_DESC, or with the blur
   const int nops = pr[0];
+  const int blur_r = desc == CLIPK_COLORBLUR_DESC ? pr[CLIPK_COLOR_DESC] : -1;
 
   if (LDS) {
     for (int g = threadIdx.x; g < ng; g += kColorThreads)
@@ -202,6 +210,21 @@ __global__ __launch_bounds__(kColorThreads) void color_kernel(int S, uint8_t* __
     }
   }
 
+  if (blur_r >= 0) {
+    const uint32_t ww = (uint32_t)pr[CLIPK_COLOR_DESC + 1], fw = (uint32_t)pr[CLIPK_COLOR_DESC + 2];
+    __syncthreads();  // every lane's pixels are in img
+    for (int l = threadIdx.x; l < 3 * S; l += kColorThreads) {
+      uint8_t* row = img + (size_t)(l / S) * P + (size_t)(l % S) * S;
+      for (int pass = 0; pass < 3; ++pass) color::box_line(row, S, 1, blur_r, ww, fw);
+    }
+    __syncthreads();
+    for (int l = threadIdx.x; l < 3 * S; l += kColorThreads) {
+      uint8_t* col = img + (size_t)(l / S) * P + l % S;
+      for (int pass = 0; pass < 3; ++pass) color::box_line(col, S, S, blur_r, ww, fw);
+    }
+    __syncthreads();
+  }
+
   for (int g = threadIdx.x; g < ng; g += kColorThreads) {
     const int i = 4 * g;
     for (int c = 0; c < 3; ++c) {
@@ -253,12 +276,14 @@ extern "C" int clipk_image_resample(int B, int S, int rows_max, const void* src,
   return CLIPK_OK;
 }
 
-extern "C" int clipk_image_color(int B, int S, void* pix, const int* prog, int* prog_dev, const float* mean,
-                                 const float* stdv, int out_uint8, void* out, void* stream) {
+// The host checks of both colour entries (nothing is launched or copied before they pass) and the
+// launch; desc: ints per image, CLIPK_COLOR_DESC or CLIPK_COLORBLUR_DESC.
+static int color_launch(int B, int S, int desc, void* pix, const int* prog, int* prog_dev, const float* mean,
+                        const float* stdv, int out_uint8, void* out, void* stream) {
   if (!pix || !prog || !prog_dev || !out || out == pix || (!out_uint8 && (!mean || !stdv))) return CLIPK_EINVAL;
   if (B < 0 || S <= 0 || S > 4096) return CLIPK_ESHAPE;
   for (int b = 0; b < B; ++b) {
-    const int* p = prog + (size_t)b * CLIPK_COLOR_DESC;
+    const int* p = prog + (size_t)b * desc;
     if (p[0] < 0 || p[0] > CLIPK_COLOR_MAX_OPS) return CLIPK_ESHAPE;
     for (int k = 0; k < p[0]; ++k) {
       const int op = p[1 + k], ip = p[1 + CLIPK_COLOR_MAX_OPS + k];
@@ -272,19 +297,35 @@ extern "C" int clipk_image_color(int B, int S, void* pix, const int* prog, int* 
         return CLIPK_EINVAL;
       }
     }
+    if (desc == CLIPK_COLORBLUR_DESC) {
+      const long long r = p[CLIPK_COLOR_DESC], ww = p[CLIPK_COLOR_DESC + 1], fw = p[CLIPK_COLOR_DESC + 2];
+      if (r < -1 || r > CLIPK_BLUR_MAX_RADIUS) return CLIPK_EINVAL;
+      if (r >= 0 && (ww <= 0 || ww > (1ll << 24) || fw < 0 || (2 * r + 1) * ww + 2 * fw > (1ll << 24)))
+        return CLIPK_EINVAL;
+    }
   }
   if (B == 0) return CLIPK_OK;
   hipStream_t st = (hipStream_t)stream;
   // pageable host memory: staged before the call returns, so prog may be freed or reused at once
-  hipError_t e = hipMemcpyAsync(prog_dev, prog, (size_t)B * CLIPK_COLOR_DESC * sizeof(int), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(prog_dev, prog, (size_t)B * desc * sizeof(int), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return (int)e;
   const size_t n4 = ((size_t)S * S + 3) / 4 * 4;
   if (3 * n4 <= (size_t)kColorLdsBytes)
     hipLaunchKernelGGL(color_kernel<true>, dim3((unsigned)B), dim3(kColorThreads), 0, st, S, (uint8_t*)pix,
-                       (const int*)prog_dev, mean, stdv, out_uint8, out);
+                       (const int*)prog_dev, desc, mean, stdv, out_uint8, out);
   else
     hipLaunchKernelGGL(color_kernel<false>, dim3((unsigned)B), dim3(kColorThreads), 0, st, S, (uint8_t*)pix,
-                       (const int*)prog_dev, mean, stdv, out_uint8, out);
+                       (const int*)prog_dev, desc, mean, stdv, out_uint8, out);
   CLIPK_CHECK_LAUNCH();
   return CLIPK_OK;
+}
+
+extern "C" int clipk_image_color(int B, int S, void* pix, const int* prog, int* prog_dev, const float* mean,
+                                 const float* stdv, int out_uint8, void* out, void* stream) {
+  return color_launch(B, S, CLIPK_COLOR_DESC, pix, prog, prog_dev, mean, stdv, out_uint8, out, stream);
+}
+
+extern "C" int clipk_image_color_blur(int B, int S, void* pix, const int* prog, int* prog_dev, const float* mean,
+                                      const float* stdv, int out_uint8, void* out, void* stream) {
+  return color_launch(B, S, CLIPK_COLORBLUR_DESC, pix, prog, prog_dev, mean, stdv, out_uint8, out, stream);
 }

@@ -30,7 +30,8 @@ k-th image the same crop as rank 0's. Data parallel: one stream per rank (seed +
 replicated batches: one stream shared by every rank (they must preprocess identically).
 The colour draws (INPUT.TRANSFORMS colorjitter / randomgrayscale, or the SimCLR distortion that
 NATIVE.SIMCLR_COLOR adds to a two-view objective's training transform: data/preprocess.py
-GpuTransform) come from the same generator, per view after its crop and flip draws.
+GpuTransform) come from the same generator, per view after its crop and flip draws, and the
+blur draws (pil_gaussian_blur, NATIVE.SIMCLR_BLUR: a coin, then sigma) after the colour draws.
 IVLP's mixup draws (``mixup``, ``draw_mix``: lam and the batch permutation) come from the same
 generator after the batch's crop draws, so replicated ranks draw the same mix and sharded ranks
 each mix their local batch.

@@ -23,6 +23,14 @@ convert("HSV"), convert("L")). Here each image carries a short program of ops, d
 uint8 pixels and writes the normalised fp32 -- every byte Pillow's (tests/test_color_*.py). With
 no colour op configured nothing changes: the resample kernel writes fp32 directly.
 
+Gaussian blur (the ``pil_gaussian_blur`` choice and NATIVE.SIMCLR_BLUR; the MoCo-v2 form
+``RandomApply([GaussianBlur(sigma ~ U(lo, hi))], p)`` with ``img.filter(ImageFilter.GaussianBlur(
+radius=sigma))``): Pillow approximates the Gaussian by three box passes of a fractional radius per
+axis, in 24-bit fixed point on uint8 images. The host derives the pass constants from sigma as
+Pillow's C does (``gaussian_blur_params``); the colour kernel runs the passes on the image it
+already holds, after its colour program (clipk_image_color_blur: still one launch) -- every byte
+Pillow's (tests/test_blur_*.py). With no blur drawn in a batch the call is the one made before.
+
 Random crop parameters and the flip coin use a torch CPU generator (the transform's own, or
 the global one) in torchvision's call order (RandomResizedCrop.get_params,
 RandomHorizontalFlip), restated here: torchvision is not installed, so that sequence is
@@ -184,34 +192,98 @@ def pack_color_programs(programs):
     return desc
 
 
-def color_batch(pix, programs, mean=MEAN, std=STD, out_uint8=False):
+def gaussian_blur_params(sigma):
+    """PIL.ImageFilter.GaussianBlur(radius=sigma) as the constants of its box passes -> (r, ww, fw):
+    the integer box radius, and the 24-bit fixed-point weights of the 2r + 1 inner samples and of
+    the two outer ones (libImaging BoxBlur.c: _gaussian_blur_radius with 3 passes, then
+    ImagingLineBoxBlur8's ww / fw). Every variable and every operation is single precision and
+    rounds on its own, as in the C source; only the sqrt and the floor run in double. The fp32
+    division behind ww matters: in double, sigma = 1.0 gives 11184810 where Pillow has 11184811."""
+    f = np.float32
+    s = f(sigma)
+    if not (s >= 0) or not np.isfinite(s):
+        raise ValueError(f"a blur sigma must be finite and non negative, got {sigma}")
+    sigma2 = s * s / f(3)
+    big_l = f(math.sqrt(12.0 * float(sigma2) + 1.0))
+    l = f(math.floor((float(big_l) - 1.0) / 2.0))
+    a = (f(2) * l + f(1)) * (l * (l + f(1)) - f(3) * sigma2)
+    a = a / (f(6) * (sigma2 - (l + f(1)) * (l + f(1))))
+    radius = l + a
+    r = int(radius)
+    ww = int(f(1 << 24) / (radius * f(2) + f(1)))
+    fw = ((1 << 24) - (2 * r + 1) * ww) // 2
+    return r, ww, fw
+
+
+def blur_sigma_range(value):
+    """INPUT.GB_SIGMA -> (lo, hi). ValueError unless it is a pair with 0 <= lo <= hi whose upper end
+    stays within the kernel's largest box radius (BLUR_MAX_RADIUS = 7: sigma below about 8.49)."""
+    if not isinstance(value, (tuple, list)) or len(value) != 2:
+        raise ValueError(f"GB_SIGMA must be a (lo, hi) pair, got {value!r}")
+    lo, hi = float(value[0]), float(value[1])
+    if not 0.0 <= lo <= hi or not math.isfinite(hi):
+        raise ValueError(f"GB_SIGMA needs 0 <= lo <= hi, got {value!r}")
+    if gaussian_blur_params(hi)[0] > N.BLUR_MAX_RADIUS:
+        raise ValueError(f"GB_SIGMA's upper end {hi} gives a box radius above {N.BLUR_MAX_RADIUS}")
+    return lo, hi
+
+
+def pack_color_blur_programs(programs, blur):
+    """Host descriptors of clipk_image_color_blur: int32 [B, COLORBLUR_DESC] -- pack_color_programs'
+    12 ints, then per image r (-1: no blur), ww, fw (gaussian_blur_params of its sigma) and a zero.
+    blur: one sigma or None per image."""
+    blur = list(blur)
+    if len(blur) != len(programs):
+        raise ValueError("blur must hold one sigma or None per program")
+    desc = np.zeros((len(programs), N.COLORBLUR_DESC), np.int32)
+    desc[:, :N.COLOR_DESC] = pack_color_programs(programs)
+    for b, sigma in enumerate(blur):
+        if sigma is None:
+            desc[b, N.COLOR_DESC] = -1
+            continue
+        r, ww, fw = gaussian_blur_params(sigma)
+        if r > N.BLUR_MAX_RADIUS:
+            raise ValueError(f"sigma {sigma} gives the box radius {r}, above {N.BLUR_MAX_RADIUS}")
+        desc[b, N.COLOR_DESC:N.COLOR_DESC + 3] = (r, ww, fw)
+    return desc
+
+
+def color_batch(pix, programs, mean=MEAN, std=STD, out_uint8=False, blur=None):
     """clipk_image_color on uint8 planar pixels [B, 3, S, S] (a CUDA tensor, contiguous): program b
     runs on image b, then ToTensor + Normalize -> fp32 [B, 3, S, S], or the uint8 pixels when
-    out_uint8. One launch. `pix` is scratch: unspecified afterwards when the image does not fit LDS."""
+    out_uint8. One launch. `pix` is scratch: unspecified afterwards when the image does not fit LDS.
+    blur: one sigma or None per image; where any is set the launch is clipk_image_color_blur, which
+    blurs those images after their programs (GaussianBlur(radius=sigma)); None or all None: the
+    call made without the argument."""
     if pix.dtype != torch.uint8 or pix.dim() != 4 or pix.shape[1] != 3 or pix.shape[2] != pix.shape[3]:
         raise ValueError("pix must be uint8 [B, 3, S, S]")
     if not pix.is_contiguous() or len(programs) != pix.shape[0]:
         raise ValueError("pix must be contiguous, with one program per image")
+    if blur is not None and len(blur) != len(programs):
+        raise ValueError("blur must hold one sigma or None per image")
     B, S, dev = int(pix.shape[0]), int(pix.shape[2]), pix.device
-    desc = pack_color_programs(programs)
-    d_prog = torch.empty(max(B, 1) * N.COLOR_DESC, dtype=torch.int32, device=dev)
+    blurred = blur is not None and any(s is not None for s in blur)
+    desc = pack_color_blur_programs(programs, blur) if blurred else pack_color_programs(programs)
+    d_prog = torch.empty(max(B, 1) * desc.shape[1], dtype=torch.int32, device=dev)
     out = torch.empty(B, 3, S, S, device=dev, dtype=torch.uint8 if out_uint8 else torch.float32)
     mean_t = torch.tensor(mean, dtype=torch.float32, device=dev)
     std_t = torch.tensor(std, dtype=torch.float32, device=dev)
-    N.call("clipk_image_color", B, S, ops._p(pix), desc.ctypes.data, ops._p(d_prog), ops._p(mean_t), ops._p(std_t),
-           1 if out_uint8 else 0, ops._p(out), ops._stream())
+    N.call("clipk_image_color_blur" if blurred else "clipk_image_color", B, S, ops._p(pix), desc.ctypes.data,
+           ops._p(d_prog), ops._p(mean_t), ops._p(std_t), 1 if out_uint8 else 0, ops._p(out), ops._stream())
     return out
 
 
 class Plan:
     """One image's geometry: source window (x0, y0, w, h) resized to (rw, rh), output
     window (ox, oy, S, S) of the resized image, horizontal flip; `color`: the colour program
-    [(op, value), ...] that runs after them (empty: none)."""
+    [(op, value), ...] that runs after them (empty: none); `blur`: the sigma of the Gaussian blur
+    that runs last (None: none)."""
 
-    def __init__(self, x0, y0, w, h, rw, rh, ox, oy, S, flip, color=()):
+    def __init__(self, x0, y0, w, h, rw, rh, ox, oy, S, flip, color=(), blur=None):
         self.x0, self.y0, self.w, self.h = x0, y0, w, h
         self.rw, self.rh, self.ox, self.oy, self.S, self.flip = rw, rh, ox, oy, S, flip
         self.color = list(color)
+        self.blur = blur
 
 
 def test_plan(w, h, size):
@@ -249,7 +321,7 @@ def _tables(plans, shapes):
 
 
 def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8=False, src_index=None,
-                     color=None):
+                     color=None, blur=None):
     """images: list of uint8 HWC (RGB) numpy arrays or CPU/GPU torch tensors; plans: Plan
     per image (all with the same S). Returns fp32 [B, 3, S, S] normalised on `device` (or
     the uint8 resampled pixels [B, 3, S, S] when out_uint8, for bit-exact checks).
@@ -257,7 +329,9 @@ def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8
     images, each uploaded once: the two views of a SimCLR batch); None: plans[k] reads images[k].
     color: one colour program per plan (color_params' form), run after crop and flip. When any is
     non-empty the resample writes uint8 and clipk_image_color writes the output (one more launch);
-    None or all empty: the resample kernel writes the output itself, as without the argument."""
+    None or all empty: the resample kernel writes the output itself, as without the argument.
+    blur: one sigma or None per plan, GaussianBlur(radius=sigma) after the colour program, in the
+    colour launch (clipk_image_color_blur; color_batch). None or all None: as without the argument."""
     dev = torch.device(device)
     S = plans[0].S
     if any(p.S != S for p in plans):
@@ -269,7 +343,12 @@ def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8
     color = None if color is None else [list(c) for c in color]
     if color is not None and len(color) != len(plans):
         raise ValueError("color must hold one program per plan")
-    staged = color is not None and any(color)
+    blur = None if blur is None else list(blur)
+    if blur is not None and len(blur) != len(plans):
+        raise ValueError("blur must hold one sigma or None per plan")
+    if blur is not None and all(s is None for s in blur):
+        blur = None
+    staged = (color is not None and any(color)) or blur is not None
     src_index = [int(k) for k in (range(len(plans)) if src_index is None else src_index)]
     if len(src_index) != len(plans) or any(not 0 <= k < len(ts) for k in src_index):
         raise ValueError("src_index must name one source image per plan")
@@ -294,7 +373,7 @@ def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8
     N.call("clipk_image_resample", B, S, rows_max, ops._p(src), ops._p(d_desc), ops._p(d_tab), ops._p(tmp),
            ops._p(mean_t), ops._p(std_t), 1 if to_u8 else 0, ops._p(out), ops._stream())
     if staged:
-        return color_batch(out, color, mean, std, out_uint8)
+        return color_batch(out, color if color is not None else [[]] * B, mean, std, out_uint8, blur)
     return out
 
 
@@ -306,13 +385,22 @@ class GpuTransform:
     the reference's order: crop, flip, colour, grayscale, ToTensor, Normalize. With
     NATIVE.SIMCLR_COLOR and a two-view objective (data/manager.py two_views) the training transform
     carries the SimCLR distortion whatever INPUT.TRANSFORMS says: the jitter under
-    RandomApply(NATIVE.SIMCLR_COLOR_P), then RandomGrayscale(INPUT.RGS_P)."""
+    RandomApply(NATIVE.SIMCLR_COLOR_P), then RandomGrayscale(INPUT.RGS_P).
+    pil_gaussian_blur (this package's choice, the MoCo-v2 form; training only): RandomApply(INPUT.GB_P)
+    around PIL's ImageFilter.GaussianBlur(radius = sigma), sigma ~ U(INPUT.GB_SIGMA), last in the
+    uint8 chain; NATIVE.SIMCLR_BLUR gives it to the two views of a two-view objective under
+    RandomApply(NATIVE.SIMCLR_BLUR_P), with or without SIMCLR_COLOR. Dassl's gaussian_blur stays
+    unimplemented: current Dassl wires that name to torchvision's GaussianBlur(kernel_size=GB_K), a
+    float convolution and another function than Pillow's filter."""
 
     def __init__(self, cfg, is_train, device="cuda", generator=None):
         choices = list(cfg.INPUT.TRANSFORMS)
-        allowed = {"random_resized_crop", "random_flip", "normalize", "colorjitter", "randomgrayscale"}
+        allowed = {"random_resized_crop", "random_flip", "normalize", "colorjitter", "randomgrayscale",
+                   "pil_gaussian_blur"}
         if is_train and not set(choices) <= allowed:
-            raise NotImplementedError(f"GPU transforms implement {sorted(allowed)}, got {choices}")
+            hint = (" (gaussian_blur, torchvision's convolution, is not built: pil_gaussian_blur is Pillow's "
+                    "ImageFilter.GaussianBlur)" if "gaussian_blur" in choices else "")
+            raise NotImplementedError(f"GPU transforms implement {sorted(allowed)}, got {choices}{hint}")
         if cfg.INPUT.INTERPOLATION != "bicubic":
             raise NotImplementedError("GPU transforms implement bicubic interpolation")
         self.is_train = is_train
@@ -328,8 +416,15 @@ class GpuTransform:
         # colour stage (training only): jitter ranges (None: no jitter), the RandomApply probability
         # around it (>= 1: no coin is drawn) and RandomGrayscale's probability (None: not configured)
         self.jitter, self.jitter_p, self.gray_p = None, 1.0, None
+        # blur (training only): the sigma range (None: no blur) and the RandomApply probability around it
+        self.blur_sigma, self.blur_p = None, 1.0
         if is_train:
             from .manager import two_views
+            simclr_blur = bool(cfg.get("NATIVE", {}).get("SIMCLR_BLUR", False)) and two_views(cfg)
+            if simclr_blur or "pil_gaussian_blur" in choices:
+                self.blur_sigma = blur_sigma_range(cfg.INPUT.get("GB_SIGMA", (0.1, 2.0)))
+                self.blur_p = float(cfg.NATIVE.get("SIMCLR_BLUR_P", 0.5) if simclr_blur
+                                    else cfg.INPUT.get("GB_P", 0.5))
             simclr = bool(cfg.get("NATIVE", {}).get("SIMCLR_COLOR", False)) and two_views(cfg)
             if simclr or "colorjitter" in choices:
                 inp = cfg.INPUT
@@ -352,6 +447,16 @@ class GpuTransform:
             prog.append((N.COLOR_GRAYSCALE, 0))
         return prog
 
+    def blur_draw(self):
+        """One image's blur draws, after its colour draws: the RandomApply coin (torch.rand(1); skipped
+        when p < coin; none at p >= 1), then, if the blur is applied, sigma =
+        torch.empty(1).uniform_(lo, hi). Draws nothing and returns None when no blur is configured."""
+        if self.blur_sigma is None:
+            return None
+        if self.blur_p < 1.0 and self.blur_p < float(torch.rand(1, generator=self.generator)):
+            return None
+        return float(torch.empty(1).uniform_(self.blur_sigma[0], self.blur_sigma[1], generator=self.generator))
+
     def plan(self, w, h):
         if not self.is_train:
             return test_plan(w, h, self.size)
@@ -363,6 +468,7 @@ class GpuTransform:
             if self.flip:
                 p.flip = bool(torch.rand(1, generator=self.generator) < 0.5)
         p.color = self.color_program()
+        p.blur = self.blur_draw()
         return p
 
     def plans(self, sizes, views=1):
@@ -373,17 +479,18 @@ class GpuTransform:
     def __call__(self, images, views=1):
         """views=1: the transformed batch [B, 3, S, S]. views=2 (SimCLR): two independent draws of
         the transform per image -> (x1, x2), the two halves of ONE [2B, 3, S, S] output (no copy);
-        the pixels are uploaded once and one resample launch (and, with colour ops, one colour launch)
-        covers both views."""
+        the pixels are uploaded once and one resample launch (and, with colour ops or blur, one
+        colour / blur launch) covers both views."""
         sizes = [(int(im.shape[1]), int(im.shape[0])) for im in images]
         if views == 1:
             drawn = self.plans(sizes)
-            return preprocess_batch(images, drawn, self.mean, self.std, self.device, color=[p.color for p in drawn])
+            return preprocess_batch(images, drawn, self.mean, self.std, self.device, color=[p.color for p in drawn],
+                                    blur=[p.blur for p in drawn])
         if views != 2:
             raise ValueError(f"views must be 1 or 2, got {views}")
         B = len(sizes)
         drawn = self.plans(sizes, 2)  # image-major
         drawn = drawn[0::2] + drawn[1::2]
         out = preprocess_batch(images, drawn, self.mean, self.std, self.device, src_index=list(range(B)) * 2,
-                               color=[p.color for p in drawn])
+                               color=[p.color for p in drawn], blur=[p.blur for p in drawn])
         return out[:B], out[B:]

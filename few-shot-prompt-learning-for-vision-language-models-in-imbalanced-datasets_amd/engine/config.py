@@ -107,7 +107,13 @@ def get_cfg_default() -> CfgNode:
                   # is this package's: the probability of a RandomApply around the jitter (1.0: the
                   # bare ColorJitter, no coin drawn)
                   "COLORJITTER_B": 0.4, "COLORJITTER_C": 0.4, "COLORJITTER_S": 0.4, "COLORJITTER_H": 0.1,
-                  "COLORJITTER_P": 1.0, "RGS_P": 0.2},
+                  "COLORJITTER_P": 1.0, "RGS_P": 0.2,
+                  # the pil_gaussian_blur choice of TRANSFORMS (training only, this package's name and
+                  # definition, the MoCo-v2 form): RandomApply(GB_P) around Pillow's
+                  # ImageFilter.GaussianBlur(radius = sigma), sigma ~ U(GB_SIGMA), last in the uint8
+                  # chain. Dassl's gaussian_blur (torchvision's float convolution) is a different
+                  # function and stays unimplemented
+                  "GB_P": 0.5, "GB_SIGMA": (0.1, 2.0)},
         "DATASET": {"ROOT": "", "NAME": "", "NUM_SHOTS": -1, "PER_CLASS_SHOTS": [],
                     "SUBSAMPLE_CLASSES": "all"},
         "DATALOADER": {"NUM_WORKERS": 8, "TRAIN_X": {"SAMPLER": "RandomSampler", "BATCH_SIZE": 32},
@@ -184,6 +190,12 @@ def get_cfg_default() -> CfgNode:
                    # RandomGrayscale(INPUT.RGS_P), on the GPU (clipk_image_color). Off: the views are
                    # two draws of crop + flip, bit for bit as before
                    "SIMCLR_COLOR": False, "SIMCLR_COLOR_P": 0.8,
+                   # SIMCLR_BLUR: the two views of a SimCLR objective also get the blur half of the
+                   # recipe, whatever INPUT.TRANSFORMS says and independent of SIMCLR_COLOR:
+                   # RandomApply([GaussianBlur(sigma ~ U(INPUT.GB_SIGMA))], SIMCLR_BLUR_P), Pillow's
+                   # filter, after the colour distortion and in its launch (clipk_image_color_blur).
+                   # Off: nothing is drawn and nothing changes
+                   "SIMCLR_BLUR": False, "SIMCLR_BLUR_P": 0.5,
                    # MIXUP: IVLP trains on mixed batches as the reference's default run does
                    # (TRAINER.IVLP.USE_MIXUP / MIXUP_ALPHA): the training loader mixes every batch
                    # (clipk_mixup_images; "y_a" / "y_b" / "lam") and the mixed criterion is one native

@@ -264,6 +264,24 @@ enum { CLIPK_COLOR_MAX_OPS = 5, CLIPK_COLOR_DESC = 12 };
 int clipk_image_color(int B, int S, void* pix, const int* prog, int* prog_dev, const float* mean,
                       const float* stdv, int out_uint8, void* out, void* stream);
 
+/* clipk_image_color followed, in the same launch, by PIL.ImageFilter.GaussianBlur on the image
+ * (Pillow's approximation: three box passes of a fractional radius along x over every row, then
+ * three along y over every column, each on the uint8 output of the one before, edges repeating
+ * the edge pixel; csrc/color_ops.h box_line, DESIGN §3 "Blur"): every uint8 result is Pillow's.
+ * The arguments are clipk_image_color's, but prog is HOST int32 [B, CLIPK_COLORBLUR_DESC] and
+ * prog_dev holds B * CLIPK_COLORBLUR_DESC * 4 bytes: per image [0..11] as in clipk_image_color,
+ * [12] the integer box radius r (-1: this image is not blurred and takes clipk_image_color's path,
+ * bit for bit; 0..CLIPK_BLUR_MAX_RADIUS otherwise), [13] ww and [14] fw, the 24-bit fixed-point
+ * weights of the 2r + 1 inner samples and of the two outer ones (fsp_amd/data/preprocess.py
+ * gaussian_blur_params derives r, ww, fw from sigma as Pillow does), [15] zero. One output of a
+ * pass is (sum_inner * ww + sum_outer * fw + 2^23) >> 24 in 32 unsigned bits. The same errors as
+ * clipk_image_color, and CLIPK_EINVAL for r outside -1..CLIPK_BLUR_MAX_RADIUS or, with r >= 0,
+ * ww outside 1..2^24, fw < 0, or (2r + 1) * ww + 2 * fw > 2^24 (the 32-bit sum would overflow);
+ * checked on the host before anything is copied or launched. */
+enum { CLIPK_COLORBLUR_DESC = 16, CLIPK_BLUR_MAX_RADIUS = 7 };
+int clipk_image_color_blur(int B, int S, void* pix, const int* prog, int* prog_dev, const float* mean,
+                           const float* stdv, int out_uint8, void* out, void* stream);
+
 /* Diagnostic: per-block / per-tile s_memrealtime marks of the last GEMM launch, recorded
  * only when the process runs with CLIPK_GEMM_STAMP set (synchronises the device). */
 int clipk_gemm_stamps(void* host, size_t bytes);

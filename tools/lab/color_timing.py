@@ -1,14 +1,21 @@
-"""Times the colour stage of the SimCLR views on the GPU (DESIGN section 5 "Colour views").
+"""Times the colour and blur stage of the SimCLR views on the GPU (DESIGN section 5 "Colour views"
+and "Blurred views").
 
-  python tools/lab/color_timing.py [--out profiles/color/timing.json] [--skip-step]
+  python tools/lab/color_timing.py [--out profiles/blur/timing.json] [--skip-step]
+                                   [--parent-lib path/to/the/parent/commit's/libclipk.so]
 
 * clipk_image_color alone at B = 64, S = 224 (uint8 in, normalised fp32 out; the descriptor
   packing and its copy included, as every call pays them): the full five-op program, the same
   program without contrast (no image-wide reduction), and an empty program (load + epilogue only);
+  clipk_image_color_blur with an empty program and every image blurred, at sigma 1.0 (box radius
+  r = 0) and 1.5 (r = 1), and the five-op program followed by the r = 1 blur; with --parent-lib the
+  empty and five-op launches of another build's clipk_image_color (the parent commit's), alternated
+  with this build's in the same process;
 * the two-view GpuTransform call (32 decoded images of 500 x 375 -> two views of 224 x 224: upload,
-  resample, and with the flag the colour launch) with NATIVE.SIMCLR_COLOR off and on;
+  resample, and with a flag the colour / blur launch) with NATIVE.SIMCLR_COLOR and
+  NATIVE.SIMCLR_BLUR off and on;
 * the CoOp SimCLR train step at the shapes of DESIGN section 5 "SimCLR" (ViT-B/16, C = 1000,
-  B = 32, n_ctx 16, FUSED_SIMCLR on) fed by that transform call, flag off and on.
+  B = 32, n_ctx 16, FUSED_SIMCLR on) fed by that transform call, the flags off and on.
 
 Each variant runs `--iters` calls per block between two synchronises (host clock), the variants
 alternate block by block in one process for `--rounds` rounds, and the median block is reported
@@ -45,13 +52,14 @@ def timed(variants, iters, rounds, warm=3, unit=1e6):
     return {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in blocks.items()}
 
 
-def transform(flag, dev, seed=0):
+def transform(flag, dev, seed=0, blur=False):
     from fsp_amd.data.preprocess import GpuTransform
     from fsp_amd.engine.config import get_cfg_default
     cfg = get_cfg_default()
     cfg.TRAINER.NAME = "CoOp"
     cfg.TRAINER.COOP.LOSS_TYPE = "simclr"
     cfg.NATIVE.SIMCLR_COLOR = flag
+    cfg.NATIVE.SIMCLR_BLUR = blur
     g = torch.Generator()
     g.manual_seed(seed)
     return GpuTransform(cfg, is_train=True, device=dev, generator=g)
@@ -65,6 +73,7 @@ def main():
     ap.add_argument("--prec", default="fp32s")
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--parent-lib", default="", help="another build's libclipk.so: its clipk_image_color is timed too")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("color_timing.py needs the GPU: nothing is measured without one")
@@ -81,7 +90,31 @@ def main():
     five = [(N.COLOR_BRIGHTNESS, f[0]), (N.COLOR_CONTRAST, f[1]), (N.COLOR_SATURATION, f[2]), (N.COLOR_HUE, 17),
             (N.COLOR_GRAYSCALE, 0)]
     progs = {"five_ops": five, "no_contrast": [op for op in five if op[0] != N.COLOR_CONTRAST], "empty": []}
-    r = timed({k: (lambda p=p: P.color_batch(pix, [p] * B)) for k, p in progs.items()}, args.iters, args.rounds)
+    variants = {k: (lambda p=p: P.color_batch(pix, [p] * B)) for k, p in progs.items()}
+    for k, p, sigma in (("blur_r0", [], 1.0), ("blur_r1", [], 1.5), ("five_ops_blur_r1", five, 1.5)):
+        assert P.gaussian_blur_params(sigma)[0] == int(k[-1])
+        variants[k] = lambda p=p, sigma=sigma: P.color_batch(pix, [p] * B, blur=[sigma] * B)
+    if args.parent_lib:
+        import ctypes
+        from fsp_amd import ops
+        parent = ctypes.CDLL(os.path.abspath(args.parent_lib))
+        parent.clipk_image_color.restype, parent.clipk_image_color.argtypes = N.SIGNATURES["clipk_image_color"]
+
+        def parent_call(p):  # color_batch's work, allocations and constants included, on the other library
+            mean_t = torch.tensor(P.MEAN, dtype=torch.float32, device=dev)
+            std_t = torch.tensor(P.STD, dtype=torch.float32, device=dev)
+            desc = P.pack_color_programs([p] * B)
+            d_prog = torch.empty(B * N.COLOR_DESC, dtype=torch.int32, device=dev)
+            out = torch.empty(B, 3, S, S, device=dev, dtype=torch.float32)
+            rc = parent.clipk_image_color(B, S, ops._p(pix), desc.ctypes.data, ops._p(d_prog), ops._p(mean_t),
+                                          ops._p(std_t), 0, ops._p(out), ops._stream())
+            assert rc == 0, rc
+            return out
+
+        assert torch.equal(parent_call(five), P.color_batch(pix, [five] * B))
+        variants["parent_five_ops"] = lambda: parent_call(five)
+        variants["parent_empty"] = lambda: parent_call([])
+    r = timed(variants, args.iters, args.rounds)
     nbytes = B * 3 * S * S * (1 + 4)  # uint8 read, fp32 write
     for v in r.values():
         v["GBps_at_median"] = nbytes / v["median"] * 1e-3
@@ -89,7 +122,8 @@ def main():
 
     # 2. the two-view transform call
     images = [rs.randint(0, 256, size=(375, 500, 3), dtype=np.uint8) for _ in range(32)]
-    tf = {"off": transform(False, dev), "on": transform(True, dev)}
+    tf = {"off": transform(False, dev), "on": transform(True, dev), "blur": transform(False, dev, blur=True),
+          "color_blur": transform(True, dev, blur=True)}
     res["two_view_transform_us_B32"] = timed({k: (lambda t=t: t(images, views=2)) for k, t in tf.items()},
                                              max(args.iters // 5, 5), args.rounds)
 
