@@ -774,7 +774,7 @@ __global__ __launch_bounds__(256) void attn_bwd_long_kv(int nseq, int L, int H, 
     float l1[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) l1[r] = lse[(row0 + min(i0 + 4 * g4 + r, L - 1)) * H + h];
-    lds_fence_a();  // the previous tile's transposed reads are done
+    lds_fence();  // the previous tile's transposed reads are done
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       *reinterpret_cast<s16x8*>(tQ + r16 * TRS + 8 * g4 + 32 * kk) = q[kk];
@@ -798,7 +798,7 @@ __global__ __launch_bounds__(256) void attn_bwd_long_kv(int nseq, int L, int H, 
     }
     const s16x4 bP = pack4<TG>(P1[0], P1[1], P1[2], P1[3]);
     const s16x4 bS = pack4<TG>(dS1[0], dS1[1], dS1[2], dS1[3]);
-    lds_fence_a();
+    lds_fence();
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       dkp[t] = mfma16_t<TG>(tr_read(tQ, 4 * g4, 16 * t, lane), bS, dkp[t]);
@@ -851,7 +851,7 @@ __global__ __launch_bounds__(256) void attn_bwd_long_q(int nseq, int L, int H, i
       k[kk] = to_g8<T, TG>(*reinterpret_cast<const s16x8*>(kb + W + 8 * g4 + 32 * kk));
       v[kk] = to_g8<T, TG>(*reinterpret_cast<const s16x8*>(kb + 2 * W + 8 * g4 + 32 * kk));
     }
-    lds_fence_a();
+    lds_fence();
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) *reinterpret_cast<s16x8*>(tK + r16 * TRS + 8 * g4 + 32 * kk) = k[kk];
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
@@ -870,7 +870,7 @@ __global__ __launch_bounds__(256) void attn_bwd_long_q(int nseq, int L, int H, i
       dS2[r] = P2 * (p2[r] - D2);
     }
     const s16x4 bT = pack4<TG>(dS2[0], dS2[1], dS2[2], dS2[3]);
-    lds_fence_a();
+    lds_fence();
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = mfma16_t<TG>(tr_read(tK, 4 * g4, 16 * t, lane), bT, acc[t]);
   }
@@ -1045,23 +1045,13 @@ static int launch_fwd(int nseq, int L, int H, int causal, const void* qkv, int l
   return CLIPK_OK;
 }
 
-// 16 < L <= 64 with 16-bit operands (CoOp n_ctx 16: L_eff 23): the two-pass MFMA kernels
-// instead of the VALU attn_bwd_short (knob CLIPK_ATTN_MFMA_BWD, default on)
-static bool mfma_long_bwd() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CLIPK_ATTN_MFMA_BWD");
-    v = e ? atoi(e) : 1;
-  }
-  return v != 0;
-}
-
 template <typename T, typename TG>
 static int launch_bwd(int nseq, int L, int H, int causal, const void* qkv, int ldq,
                       const void* ofwd, int ldof, const void* dout, int lddo, const float* lse,
                       void* dqkv, int lddq, hipStream_t st) {
   const int pairs = nseq * H;
-  if constexpr (sizeof(TG) == 2 && sizeof(T) == 2) {
+  constexpr bool mfma = sizeof(TG) == 2 && sizeof(T) == 2;
+  if constexpr (mfma) {
     if (L <= 16) {
       hipLaunchKernelGGL((attn_bwd_mfma16<T, TG>), dim3((pairs + 3) / 4), dim3(256), 0, st, nseq, L, H,
                          causal, (const T*)qkv, ldq, (const TG*)dout, lddo, lse, (TG*)dqkv, lddq);
@@ -1069,9 +1059,11 @@ static int launch_bwd(int nseq, int L, int H, int causal, const void* qkv, int l
       return CLIPK_OK;
     }
   }
-  if (L > 64 || (sizeof(TG) == 2 && sizeof(T) == 2 && mfma_long_bwd())) {
+  // 16-bit operands past L = 16 (CoOp n_ctx 16: L_eff 23) always take the two-pass MFMA kernels;
+  // the VALU attn_bwd_short below serves fp32 up to L = 64
+  if (mfma || L > 64) {
     // two passes (dK/dV per key tile, dQ per query tile); MFMA for 16-bit operands
-    if constexpr (sizeof(TG) == 2 && sizeof(T) == 2) {
+    if constexpr (mfma) {
       dim3 grid((L + 63) / 64, H, nseq);
       hipLaunchKernelGGL((attn_bwd_long_kv<T, TG>), grid, dim3(256), 0, st, nseq, L, H, causal, (const T*)qkv, ldq,
                          (const T*)ofwd, ldof, (const TG*)dout, lddo, lse, (TG*)dqkv, lddq);
@@ -1089,18 +1081,19 @@ static int launch_bwd(int nseq, int L, int H, int causal, const void* qkv, int l
     CLIPK_CHECK_LAUNCH();
     return CLIPK_OK;
   }
-  auto go = [&](auto lp_tag) {
-    constexpr int LP = decltype(lp_tag)::value;
-    constexpr int G = 64 / LP;
-    const int blocks = (pairs + G - 1) / G;
-    hipLaunchKernelGGL((attn_bwd_short<LP, T, TG>), dim3(blocks), dim3(64), 0, st, nseq, L, H,
-                       causal, (const T*)qkv, ldq, (const T*)ofwd, ldof, (const TG*)dout, lddo, lse,
-                       (TG*)dqkv, lddq);
-  };
-  if (L <= 16) go(std::integral_constant<int, 16>{});
-  else if (L <= 32) go(std::integral_constant<int, 32>{});
-  else if (L <= 64) go(std::integral_constant<int, 64>{});
-  else return CLIPK_ESHAPE;
+  if constexpr (!mfma) {
+    auto go = [&](auto lp_tag) {
+      constexpr int LP = decltype(lp_tag)::value;
+      constexpr int G = 64 / LP;
+      const int blocks = (pairs + G - 1) / G;
+      hipLaunchKernelGGL((attn_bwd_short<LP, T, TG>), dim3(blocks), dim3(64), 0, st, nseq, L, H,
+                         causal, (const T*)qkv, ldq, (const T*)ofwd, ldof, (const TG*)dout, lddo, lse,
+                         (TG*)dqkv, lddq);
+    };
+    if (L <= 16) go(std::integral_constant<int, 16>{});
+    else if (L <= 32) go(std::integral_constant<int, 32>{});
+    else go(std::integral_constant<int, 64>{});
+  }
   CLIPK_CHECK_LAUNCH();
   return CLIPK_OK;
 }

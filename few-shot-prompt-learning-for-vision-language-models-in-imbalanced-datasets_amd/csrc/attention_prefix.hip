@@ -28,18 +28,34 @@
 
 namespace clipk {
 
-// tiles whose loads are issued together (template parameter; env CLIPK_PREFIX_*_BATCH)
 constexpr int kValuChunkMin = 4;              // units per wave, fp32 kernels: at least (f32_uc)
 
-// Units per wave of the MFMA kernels (env CLIPK_PREFIX_FWD_CHUNK / _BWD_CHUNK, read once).
+// The configuration of the 16-bit kernels: the winners of the sweeps at the bench shape (G 8,
+// C 1000, P 5; clean-cache HIP events, tools/attn_sweep.py). The losing variants are not built.
+// LDS ring slots per wave: 2. LDS-staged against register-operand kernels: backward 98.4 ->
+// 82.4 us (0.50 -> 0.60 of HBM), forward 48.4 -> 43.0 us; 3 slots at 4 waves: forward 48.2
+// against 44.2 us, backward equal (profiles/r02h_attn_sweep.txt); 3 and 4 slots at 1 and 2
+// waves slower in both (profiles/r02p_attn_ring_sweep.txt)
+constexpr int kLdsSlots = 2;
+// LDS-staged kernels, waves per block: 4 (1 and 2: backward 96-98 us against 82; 8 no better,
+// profiles/r02p_attn_ring_sweep.txt)
+constexpr int kLdsWpb = 4;
+// register-operand backward, waves per block: 4 (8 -- all heads of a row range in one block --
+// 98.2 against 98.4 us, profiles/r02h_attn_sweep.txt)
+constexpr int kRegWpb = 4;
+// register-operand backward, tiles whose loads are issued together: 2 (tuned with the 16-row
+// tile packing; no profile kept)
+constexpr int kRegBwdBatch = 2;
+
+// Units per wave of the MFMA kernels (env CLIPK_PREFIX_FWD_CHUNK / _BWD_CHUNK, read once). They
+// pick no kernel (uc is a runtime argument); the tests reach 1- and 3-unit chunks through them.
 static int chunk_env(const char* name, int def) {
   const char* e = getenv(name);
   const int v = e ? atoi(e) : def;
   return v >= 1 && v <= 16 ? v : def;
 }
-static int lds_slots();
-// (the LDS-staged forward measured best at 4 units per wave, the register one at 8)
-static int fwd_chunk() { static int c = chunk_env("CLIPK_PREFIX_FWD_CHUNK", lds_slots() ? 4 : 8); return c; }
+// (the LDS-staged forward measured best at 4 units per wave)
+static int fwd_chunk() { static int c = chunk_env("CLIPK_PREFIX_FWD_CHUNK", 4); return c; }
 static int bwd_chunk() { static int c = chunk_env("CLIPK_PREFIX_BWD_CHUNK", 16); return c; }
 static int prefix_num_cus() {
   static int n = 0;
@@ -70,38 +86,10 @@ static int f32_uc(int G, int ntiles, int H, int wpc) {
   // at most 16: many groups (the eval's 100 images) keep several rounds of shorter waves
   return (int)(uc < kValuChunkMin ? kValuChunkMin : uc > 16 ? 16 : uc);
 }
-// resident waves per CU of the fp32 kernels at WPB = 2 (VGPRs: forward 146 -> 3 per SIMD,
+// resident waves per CU of the fp32 kernels at 2 waves per block (kF32Wpb; VGPRs: forward 146 -> 3 per SIMD,
 // backward <= 256 -> 2; LDS: forward 24 KB, backward 34 KB per 2-wave block)
 constexpr int kF32FwdWpc = 12, kF32BwdWpc = 8;
-static int fwd_batch() { static int c = chunk_env("CLIPK_PREFIX_FWD_BATCH", 1); return c; }
-static int bwd_batch() { static int c = chunk_env("CLIPK_PREFIX_BWD_BATCH", 2); return c; }
-// Waves per block (4 or 8; env CLIPK_PREFIX_WPB). Waves are head-fastest, so 8 waves (H = 8)
-// put all heads of a row range in one block: one CU reads whole qkv rows.
-static int prefix_wpb() { static int c = chunk_env("CLIPK_PREFIX_WPB", 4) >= 8 ? 8 : 4; return c; }
 static inline int n_chunks(int ntiles, int uc) { return (ntiles + 1 + uc - 1) / uc; }
-// LDS-staged kernels (attn_prefix_*_lds): ring slots per wave (CLIPK_PREFIX_LDS: 0 = the
-// register-operand kernels, 2 or 3) and waves per block (CLIPK_PREFIX_LDS_WPB: 1, 2 or 4).
-// Bench shape (G 8, C 1000, P 5; clean-cache HIP events, tools/attn_sweep.py): backward
-// 98.4 -> 82.4 us (0.50 -> 0.60 of HBM), forward 48.4 -> 43.0 us at 2 slots / 4 waves.
-static int lds_slots() {
-  static int c = -1;
-  if (c < 0) {
-    const char* e = getenv("CLIPK_PREFIX_LDS");
-    c = e ? atoi(e) : 2;
-    if (c != 0 && c != 2 && c != 3) c = 2;
-  }
-  return c;
-}
-static int lds_wpb() {
-  static int c = -1;
-  if (c < 0) {
-    const char* e = getenv("CLIPK_PREFIX_LDS_WPB");
-    c = e ? atoi(e) : 4;
-    if (c != 1 && c != 2 && c != 4) c = 4;
-  }
-  return c;
-}
-
 // The chunk's tile table in one VGPR (lane i holds tiles[2*(u_begin-1) + i]), read back
 // with v_readlane: no dependent scalar-memory round trip inside the tile loop.
 __device__ __forceinline__ int load_tile_table(const int* __restrict__ tiles, int ntiles, int u_begin,
@@ -124,130 +112,99 @@ __device__ __forceinline__ void tile_info(int tab, int P, int u, int u_begin, in
 // are masked out of P / dS, never zeroed): no exec-masked branch around the load, so the
 // compiler counts the batch's loads (vmcnt(N)) instead of draining them.
 __device__ __forceinline__ s16x8 ld16(const void* p) { return *reinterpret_cast<const s16x8*>(p); }
-__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// ------------------------------------------------------------------ forward, MFMA (16-bit)
-struct TileRows {
-  s16x8 q[2], k[2], v[2];
-  int t0, n, pre, first;  // first: this lane's row's class start, tile-relative
-};
-
-template <typename T, int kFwdBatch, int WPB = 4>
-__global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_mfma(int G, int P, int R, int ntiles,
-                                                            const int* __restrict__ tiles,
-                                                            const int* __restrict__ row_first, int H,
-                                                            int nchunk, int uc, const T* __restrict__ qkv,
-                                                            int ldq, T* __restrict__ out, int ldo,
-                                                            float* __restrict__ lse, int cls0) {
-  __shared__ CLIPK_LDS_ALIGN short sm[WPB][2][16 * TRS];  // per wave: prefix V, own V
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r16 = lane & 15, g4 = lane >> 4;
-  const int wid = blockIdx.x * WPB + w;
-  if (wid >= G * nchunk * H) return;  // wave-uniform; no block barriers below
-  const int h = wid % H, k = (wid / H) % nchunk, g = wid / (H * nchunk);
-  const int W = H * 64;
-  short* sVp = sm[w][0];
-  short* sVo = sm[w][1];
-  const int gR = g * R;
-  const T* qh = qkv + h * 64;
-
-  const int u_begin = k * uc, u_end = min((k + 1) * uc, ntiles + 1);
-  const int tab = load_tile_table(tiles, ntiles, u_begin, lane);
-  auto load = [&](int u, TileRows& f) {
-    tile_info(tab, P, u, u_begin, f.t0, f.n, f.pre);
-    const int rl = f.t0 + min(r16, f.n - 1);
-    const T* qp = qh + ((cls0 && u > 0 ? 0 : gR) + rl) * ldq;  // cls0: class rows read from group 0
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int c = 8 * g4 + 32 * kk;
-      f.q[kk] = ld16(qp + c);
-      f.k[kk] = ld16(qp + W + c);
-      f.v[kk] = ld16(qp + 2 * W + c);
-    }
-    f.first = u == 0 ? 0 : row_first[rl] - f.t0;
-  };
-
-  const bool pok = r16 < P;
-  const T* pp = qh + (gR + (pok ? r16 : 0)) * ldq;
-  s16x8 kp[2];
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-    const int c = 8 * g4 + 32 * kk;
-    kp[kk] = ld_row16(pp + W + c, pok);
-    *reinterpret_cast<s16x8*>(sVp + r16 * TRS + c) = ld_row16(pp + 2 * W + c, pok);
-  }
-  auto body = [&](TileRows& cur) {
-    const int n = cur.n, pre = cur.pre, first = cur.first;
-    const bool qok = r16 < n;
-    lds_fence();  // previous tile's transposed reads of sVo are done
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) *reinterpret_cast<s16x8*>(sVo + r16 * TRS + 8 * g4 + 32 * kk) = cur.v[kk];
-    f32x4 sp = {0.f, 0.f, 0.f, 0.f}, so = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      sp = mfma32_t<T>(kp[kk], cur.q[kk], sp);     // sp[r] = S[query r16][prefix key 4g4+r]
-      so = mfma32_t<T>(cur.k[kk], cur.q[kk], so);  // so[r] = S[query r16][own key 4g4+r]
-    }
-    float vp[4], vq[4], mx = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int key = 4 * g4 + r;
-      vp[r] = key < pre ? sp[r] * kScale : -INFINITY;
-      vq[r] = (key <= r16 && key >= first) ? so[r] * kScale : -INFINITY;  // key == r16 always valid
-      mx = fmaxf(mx, fmaxf(vp[r], vq[r]));
-    }
-    mx = xmax4(mx);
-    float ep[4], eo[4], ps = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      ep[r] = __expf(vp[r] - mx);
-      eo[r] = __expf(vq[r] - mx);
-      ps += ep[r] + eo[r];
-    }
-    ps = xsum4(ps);
-    lds_fence();
-    // O^T = V^T P^T: the transposed V read doubles as the A operand (A[m=d][k=key]) and the
-    // probabilities as B (B[k=key 4g4+jj][n=query r16]), so lane (r16, g4) ends up holding
-    // O[query r16][d = 16t + 4g4 .. +3]: one 8-byte store per 16 columns.
-    const s16x4 bp = pack4<T>(ep[0], ep[1], ep[2], ep[3]);
-    const s16x4 bo = pack4<T>(eo[0], eo[1], eo[2], eo[3]);
-    const float inv = 1.0f / ps;
-    f32x4 o[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      o[t] = mfma16_t<T>(tr_read(sVp, 4 * g4, 16 * t, lane), bp, (f32x4){0.f, 0.f, 0.f, 0.f});
-      o[t] = mfma16_t<T>(tr_read(sVo, 4 * g4, 16 * t, lane), bo, o[t]);
-    }
-    store_tile64<T>(out + (gR + cur.t0 + r16) * ldo + h * 64, o, inv, qok);
-    if (lse && g4 == 0 && qok) lse[(gR + cur.t0 + r16) * H + h] = mx + __logf(ps);
-  };
-  // Batches of tiles: all their loads issued up front (unconditional, clamped), then the
-  // bodies; waits are counted inside one loop iteration (a load carried across the back
-  // edge gets a vmcnt(0) at the loop head).
-  for (int u = u_begin; u < u_end; u += kFwdBatch) {
-    TileRows rr[kFwdBatch];
-#pragma unroll
-    for (int j = 0; j < kFwdBatch; ++j) load(min(u + j, u_end - 1), rr[j]);
-    __builtin_amdgcn_sched_barrier(0);  // every load of the batch issues before the first wait
-#pragma unroll
-    for (int j = 0; j < kFwdBatch; ++j)
-      if (u + j < u_end) body(rr[j]);
-  }
-}
-
-// ------------------------------------------------------------------ backward, MFMA (math in the grad dtype)
+// ------------------------------------------------------------------ backward, MFMA (16-bit): tile math
 // Per tile, with the two 16-key tiles (prefix, own) handled like attn_bwd_mfma16: S / dP in
 // both accumulator layouts, D_i = rowsum(P o dP) over both key tiles in registers; then the
 // transposed products (operands swapped) dV^T = dO^T P, dK^T = Q^T dS, dQ^T = K^T dS^T so
 // that each lane holds 4 consecutive columns of one row for the stores.
+// bwd_tile_operands is the part both backward kernels share: from the operand fragments of row
+// r16 (q, own k / v, dO; prefix k / v), the lse and class start (tile-relative) of row r16 (l2,
+// first2) and of rows 4g4+r (l1, first1), the packed B operands of the transposed products, in
+// the math dtype TG: P (bPp, bPo) and dS (bSp, bSo) as B[k=i][n=j], dS^T (bTp, bTo) as
+// B[k=j][n=i]; p = prefix keys, o = own keys. How the fragments are loaded, the transposed A
+// reads and the dQ / dK / dV accumulation stay with each kernel.
+template <typename TG>
+__device__ __forceinline__ void bwd_tile_operands(const s16x8 (&q)[2], const s16x8 (&ko)[2], const s16x8 (&vo)[2],
+                                                  const s16x8 (&d)[2], const s16x8 (&kp)[2], const s16x8 (&vp)[2],
+                                                  float l2, const float (&l1)[4], int first2, const int (&first1)[4],
+                                                  int n, int pre, int r16, int g4, s16x4& bPp, s16x4& bSp,
+                                                  s16x4& bPo, s16x4& bSo, s16x4& bTp, s16x4& bTo) {
+  const bool qok = r16 < n;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  f32x4 s1p = z, s2p = z, p1p = z, p2p = z, s1o = z, s2o = z, p1o = z, p2o = z;
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    s1p = mfma32_t<TG>(q[kk], kp[kk], s1p);   // S  [i=4g4+r][j=r16]
+    s2p = mfma32_t<TG>(kp[kk], q[kk], s2p);   // S^T[j=4g4+r][i=r16]
+    p1p = mfma32_t<TG>(d[kk], vp[kk], p1p);   // dP [i][j]
+    p2p = mfma32_t<TG>(vp[kk], d[kk], p2p);   // dP^T
+    s1o = mfma32_t<TG>(q[kk], ko[kk], s1o);
+    s2o = mfma32_t<TG>(ko[kk], q[kk], s2o);
+    p1o = mfma32_t<TG>(d[kk], vo[kk], p1o);
+    p2o = mfma32_t<TG>(vo[kk], d[kk], p2o);
+  }
+  // layout 2: i = r16, j = 4g4+r  (rows past the tile are clamped copies: masked, not zeroed)
+  float P2p[4], P2o[4], Dsum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int j = 4 * g4 + r;
+    P2p[r] = (qok && j < pre) ? __expf(s2p[r] * kScale - l2) : 0.f;
+    P2o[r] = (qok && j <= r16 && j >= first2) ? __expf(s2o[r] * kScale - l2) : 0.f;
+    Dsum += P2p[r] * p2p[r] + P2o[r] * p2o[r];
+  }
+  Dsum = xsum4(Dsum);  // D_i for i = r16
+  float dS2p[4], dS2o[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    dS2p[r] = P2p[r] * (p2p[r] - Dsum);
+    dS2o[r] = P2o[r] * (p2o[r] - Dsum);
+  }
+  // layout 1: i = 4g4+r, j = r16
+  float P1p[4], P1o[4], dS1p[4], dS1o[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = 4 * g4 + r;
+    const bool iok = i < n;
+    const float Di = __shfl(Dsum, i, 64);
+    P1p[r] = (iok && r16 < pre) ? __expf(s1p[r] * kScale - l1[r]) : 0.f;
+    P1o[r] = (iok && r16 <= i && r16 >= first1[r]) ? __expf(s1o[r] * kScale - l1[r]) : 0.f;
+    dS1p[r] = P1p[r] * (p1p[r] - Di);
+    dS1o[r] = P1o[r] * (p1o[r] - Di);
+  }
+  bPp = pack4<TG>(P1p[0], P1p[1], P1p[2], P1p[3]);      // B[k=i][n=j]
+  bSp = pack4<TG>(dS1p[0], dS1p[1], dS1p[2], dS1p[3]);
+  bPo = pack4<TG>(P1o[0], P1o[1], P1o[2], P1o[3]);
+  bSo = pack4<TG>(dS1o[0], dS1o[1], dS1o[2], dS1o[3]);
+  bTp = pack4<TG>(dS2p[0], dS2p[1], dS2p[2], dS2p[3]);  // B[k=j][n=i]
+  bTo = pack4<TG>(dS2o[0], dS2o[1], dS2o[2], dS2o[3]);
+}
+// a chunk's partial dK | dV of the prefix rows (fp32; pb: the chunk's [16][2W] block of part)
+__device__ __forceinline__ void store_prefix_partials(float* pb, int W, int h, int P, int r16, int g4,
+                                                      const f32x4 (&dkp)[4], const f32x4 (&dvp)[4]) {
+  if (r16 < P) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      float* dst = pb + (size_t)r16 * 2 * W + h * 64 + 16 * t + 4 * g4;
+      *reinterpret_cast<f32x4*>(dst) = dkp[t] * kScale;
+      *reinterpret_cast<f32x4*>(dst + W) = dvp[t];
+    }
+  }
+}
+
+// ------------------------------------------------------------------ backward, MFMA, register operands
+// Serves only the mixed case, operand dtype T != gradient dtype TG (fp16 operands with bf16
+// gradients): each lane loads its operand fragment straight into registers and converts it to
+// TG, the math dtype. With T == TG the LDS-staged attn_prefix_bwd_lds below runs instead (it
+// stages raw bytes, so it cannot convert).
 struct TileRowsB {
   s16x8 q[2], k[2], v[2], d[2];
   float l2, l1[4];
   int t0, n, pre, first2, first1[4];  // class starts (tile-relative) of rows r16 and 4g4+r
 };
 
-template <typename T, typename TG, int kBwdBatch, int WPB = 4>
-__global__ __launch_bounds__(WPB * 64) void attn_prefix_bwd_mfma(int G, int P, int R, int ntiles,
+template <typename T, typename TG>
+__global__ __launch_bounds__(kRegWpb * 64) void attn_prefix_bwd_mfma(int G, int P, int R, int ntiles,
                                                             const int* __restrict__ tiles,
                                                             const int* __restrict__ row_first, int H,
                                                             int nchunk, int uc, const T* __restrict__ qkv,
@@ -256,10 +213,10 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_bwd_mfma(int G, int P, i
                                                             TG* __restrict__ dqkv, int lddq,
                                                             float* __restrict__ part, int cls0) {
   static_assert(sizeof(T) == 2 && sizeof(TG) == 2, "MFMA attention backward: 16-bit operands, math in TG");
-  __shared__ CLIPK_LDS_ALIGN short sm[WPB][4][16 * TRS];  // per wave: K_pre, K_own, Q, dO
+  __shared__ CLIPK_LDS_ALIGN short sm[kRegWpb][4][16 * TRS];  // per wave: K_pre, K_own, Q, dO
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r16 = lane & 15, g4 = lane >> 4;
-  const int wid = blockIdx.x * WPB + w;
+  const int wid = blockIdx.x * kRegWpb + w;
   if (wid >= G * nchunk * H) return;  // wave-uniform
   const int h = wid % H, k = (wid / H) % nchunk, g = wid / (H * nchunk);
   const int W = H * 64;
@@ -333,52 +290,9 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_bwd_mfma(int G, int P, i
       *reinterpret_cast<s16x8*>(tD + r16 * TRS + c) = d[kk];
     }
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    f32x4 s1p = z, s2p = z, p1p = z, p2p = z, s1o = z, s2o = z, p1o = z, p2o = z;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      s1p = mfma32_t<TG>(q[kk], kp[kk], s1p);   // S  [i=4g4+r][j=r16]
-      s2p = mfma32_t<TG>(kp[kk], q[kk], s2p);   // S^T[j=4g4+r][i=r16]
-      p1p = mfma32_t<TG>(d[kk], vp[kk], p1p);   // dP [i][j]
-      p2p = mfma32_t<TG>(vp[kk], d[kk], p2p);   // dP^T
-      s1o = mfma32_t<TG>(q[kk], ko[kk], s1o);
-      s2o = mfma32_t<TG>(ko[kk], q[kk], s2o);
-      p1o = mfma32_t<TG>(d[kk], vo[kk], p1o);
-      p2o = mfma32_t<TG>(vo[kk], d[kk], p2o);
-    }
-    // layout 2: i = r16, j = 4g4+r  (rows past the tile are clamped copies: masked, not zeroed)
-    float P2p[4], P2o[4], Dsum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int j = 4 * g4 + r;
-      P2p[r] = (qok && j < pre) ? __expf(s2p[r] * kScale - cur.l2) : 0.f;
-      P2o[r] = (qok && j <= r16 && j >= cur.first2) ? __expf(s2o[r] * kScale - cur.l2) : 0.f;
-      Dsum += P2p[r] * p2p[r] + P2o[r] * p2o[r];
-    }
-    Dsum = xsum4(Dsum);  // D_i for i = r16
-    float dS2p[4], dS2o[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      dS2p[r] = P2p[r] * (p2p[r] - Dsum);
-      dS2o[r] = P2o[r] * (p2o[r] - Dsum);
-    }
-    // layout 1: i = 4g4+r, j = r16
-    float P1p[4], P1o[4], dS1p[4], dS1o[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 4 * g4 + r;
-      const bool iok = i < n;
-      const float Di = __shfl(Dsum, i, 64);
-      P1p[r] = (iok && r16 < pre) ? __expf(s1p[r] * kScale - cur.l1[r]) : 0.f;
-      P1o[r] = (iok && r16 <= i && r16 >= cur.first1[r]) ? __expf(s1o[r] * kScale - cur.l1[r]) : 0.f;
-      dS1p[r] = P1p[r] * (p1p[r] - Di);
-      dS1o[r] = P1o[r] * (p1o[r] - Di);
-    }
-    const s16x4 bPp = pack4<TG>(P1p[0], P1p[1], P1p[2], P1p[3]);      // B[k=i][n=j]
-    const s16x4 bSp = pack4<TG>(dS1p[0], dS1p[1], dS1p[2], dS1p[3]);
-    const s16x4 bPo = pack4<TG>(P1o[0], P1o[1], P1o[2], P1o[3]);
-    const s16x4 bSo = pack4<TG>(dS1o[0], dS1o[1], dS1o[2], dS1o[3]);
-    const s16x4 bTp = pack4<TG>(dS2p[0], dS2p[1], dS2p[2], dS2p[3]);  // B[k=j][n=i]
-    const s16x4 bTo = pack4<TG>(dS2o[0], dS2o[1], dS2o[2], dS2o[3]);
+    s16x4 bPp, bSp, bPo, bSo, bTp, bTo;
+    bwd_tile_operands<TG>(q, ko, vo, cur.d, kp, vp, cur.l2, cur.l1, cur.first2, cur.first1, n, pre, r16, g4, bPp, bSp,
+                          bPo, bSo, bTp, bTo);
     lds_fence();
     // one output (16 rows x 64) at a time, so only one 16-register tile is live for the
     // widened store
@@ -407,36 +321,28 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_bwd_mfma(int G, int P, i
     }
     if (!own_is_prefix) store_tile64<TG>(orow + 2 * W, acc, 1.0f, qok);  // dV
   };
-  for (int u = u_begin; u < u_end; u += kBwdBatch) {
-    TileRowsB rr[kBwdBatch];
+  for (int u = u_begin; u < u_end; u += kRegBwdBatch) {
+    TileRowsB rr[kRegBwdBatch];
 #pragma unroll
-    for (int j = 0; j < kBwdBatch; ++j) load(min(u + j, u_end - 1), rr[j]);
+    for (int j = 0; j < kRegBwdBatch; ++j) load(min(u + j, u_end - 1), rr[j]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int j = 0; j < kBwdBatch; ++j)
+    for (int j = 0; j < kRegBwdBatch; ++j)
       if (u + j < u_end) body(rr[j], u + j == 0);
   }
-  // this chunk's partial dK/dV of the prefix rows (fp32, [G][nchunk][16][2W])
-  float* pb = part + ((size_t)g * nchunk + k) * 16 * (2 * W);
-  if (r16 < P) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      float* dst = pb + (size_t)r16 * 2 * W + h * 64 + 16 * t + 4 * g4;
-      *reinterpret_cast<f32x4*>(dst) = dkp[t] * kScale;
-      *reinterpret_cast<f32x4*>(dst + W) = dvp[t];
-    }
-  }
+  store_prefix_partials(part + ((size_t)g * nchunk + k) * 16 * (2 * W), W, h, P, r16, g4, dkp, dvp);
 }
 
 // ------------------------------------------------------------------ LDS-staged MFMA kernels
-// The kernels above load each lane's operand fragment straight into registers: one load
+// The 16-bit forward, and the backward when operands and gradients share a dtype. A
+// register-operand kernel (above) loads each lane's fragment straight into registers: one load
 // instruction covers 16 rows x 64 B (half of each 128-B head slice), and a wave waits out a
 // full load latency per batch of tiles. Here a tile's head slices arrive by global_load_lds
 // (16 B per lane, lane-linear: one instruction = 8 whole 128-B rows) into a per-wave LDS ring
-// of NS slots, NS-1 tiles ahead of the one being computed, so the next tiles' bytes are in
+// of kLdsSlots slots, one tile ahead of the one being computed, so the next tile's bytes are in
 // flight during this tile's math. Per-row side data (row_first, and the backward's lse) come
-// the same way (4 B per lane), so the loop carries no register loads. The math is that of the
-// register kernels, operand for operand (bitwise-equal results).
+// the same way (4 B per lane), so the loop carries no register loads. The backward's math is
+// that of the register kernel, operand for operand (bitwise-equal results).
 // LDS tile: 16 rows x 128 B; 16-B chunk G of row r sits at slot G ^ ((r >> 1) & 7), so the
 // 16 lanes reading one chunk of rows 0..15 hit 16 distinct slots of the 256-B bank row.
 __device__ __forceinline__ int tsw(int r) { return (r >> 1) & 7; }
@@ -503,8 +409,8 @@ __device__ __forceinline__ void tr_read4_pad(const short* tile, int rbase, int l
 
 template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-template <typename T, int NS, int WPB>
-__global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_lds(int G, int P, int R, int ntiles,
+template <typename T>
+__global__ __launch_bounds__(kLdsWpb * 64) void attn_prefix_fwd_lds(int G, int P, int R, int ntiles,
                                                            const int* __restrict__ tiles,
                                                            const int* __restrict__ row_first, int H,
                                                            int nchunk, int uc, const T* __restrict__ qkv,
@@ -512,15 +418,15 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_lds(int G, int P, in
                                                            float* __restrict__ lse, int cls0) {
   constexpr int SLOT = 3 * 2048 + 256;  // q | k | v tiles, row_first of the 16 rows (+ lane copies)
   constexpr int PER = 7;                // global_load_lds per tile
-  __shared__ CLIPK_LDS_ALIGN char sm[WPB][NS * SLOT + 16 * TRS * 2];
+  __shared__ CLIPK_LDS_ALIGN char sm[kLdsWpb][kLdsSlots * SLOT + 16 * TRS * 2];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r16 = lane & 15, g4 = lane >> 4;
-  const int wid = blockIdx.x * WPB + w;
+  const int wid = blockIdx.x * kLdsWpb + w;
   if (wid >= G * nchunk * H) return;  // wave-uniform; no block barriers below
   const int h = wid % H, k = (wid / H) % nchunk, g = wid / (H * nchunk);
   const int W = H * 64;
   char* ring = sm[w];
-  short* sVp = reinterpret_cast<short*>(ring + NS * SLOT);
+  short* sVp = reinterpret_cast<short*>(ring + kLdsSlots * SLOT);
   const int gR = g * R;
   const T* qh = qkv + h * 64;
   const int u_begin = k * uc, u_end = min((k + 1) * uc, ntiles + 1);
@@ -544,18 +450,18 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_lds(int G, int P, in
   }
   const int nu = u_end - u_begin;
 #pragma unroll
-  for (int d = 0; d < NS - 1; ++d)
+  for (int d = 0; d < kLdsSlots - 1; ++d)
     if (d < nu) issue(u_begin + d, d);
   for (int i = 0; i < nu; ++i) {
     const int u = u_begin + i;
-    // ring: tile i+NS-1 goes into the slot tile i-1 was read from (its reads retired)
+    // ring: tile i+kLdsSlots-1 goes into the slot tile i-1 was read from (its reads retired)
     lds_fence();
-    if (i + NS - 1 < nu) issue(u + NS - 1, (i + NS - 1) % NS);
-    const int ahead = min(NS - 1, nu - 1 - i);  // tiles issued after tile i
-    if (ahead >= 2) vm_wait<2 * PER>();
-    else if (ahead == 1) vm_wait<PER>();
+    if (i + kLdsSlots - 1 < nu) issue(u + kLdsSlots - 1, (i + kLdsSlots - 1) % kLdsSlots);
+    static_assert(kLdsSlots == 2, "the wait below: at most one tile issued after tile i");
+    const int ahead = min(kLdsSlots - 1, nu - 1 - i);  // tiles issued after tile i
+    if (ahead == 1) vm_wait<PER>();
     else vm_wait<0>();
-    const char* b = ring + (i % NS) * SLOT;
+    const char* b = ring + (i % kLdsSlots) * SLOT;
     int t0, n, pre;
     tile_info(tab, P, u, u_begin, t0, n, pre);
     const int first = u == 0 ? 0 : reinterpret_cast<const int*>(b + 3 * 2048)[r16] - t0;
@@ -569,15 +475,15 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_lds(int G, int P, in
     f32x4 sp = {0.f, 0.f, 0.f, 0.f}, so = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      sp = mfma32_t<T>(kp[kk], q[kk], sp);
-      so = mfma32_t<T>(ko[kk], q[kk], so);
+      sp = mfma32_t<T>(kp[kk], q[kk], sp);  // sp[r] = S[query r16][prefix key 4g4+r]
+      so = mfma32_t<T>(ko[kk], q[kk], so);  // so[r] = S[query r16][own key 4g4+r]
     }
     float vp[4], vq[4], mx = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int key = 4 * g4 + r;
       vp[r] = key < pre ? sp[r] * kScale : -INFINITY;
-      vq[r] = (key <= r16 && key >= first) ? so[r] * kScale : -INFINITY;
+      vq[r] = (key <= r16 && key >= first) ? so[r] * kScale : -INFINITY;  // key == r16 always valid
       mx = fmaxf(mx, fmaxf(vp[r], vq[r]));
     }
     mx = xmax4(mx);
@@ -589,6 +495,9 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_lds(int G, int P, in
       ps += ep[r] + eo[r];
     }
     ps = xsum4(ps);
+    // O^T = V^T P^T: the transposed V read doubles as the A operand (A[m=d][k=key]) and the
+    // probabilities as B (B[k=key 4g4+jj][n=query r16]), so lane (r16, g4) ends up holding
+    // O[query r16][d = 16t + 4g4 .. +3] (store_tile64 regroups them into 16-B stores).
     const s16x4 bp = pack4<T>(ep[0], ep[1], ep[2], ep[3]);
     const s16x4 bo = pack4<T>(eo[0], eo[1], eo[2], eo[3]);
     const float inv = 1.0f / ps;
@@ -606,8 +515,8 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_lds(int G, int P, in
   }
 }
 
-template <typename T, int NS, int WPB>
-__global__ __launch_bounds__(WPB * 64) void attn_prefix_bwd_lds(int G, int P, int R, int ntiles,
+template <typename T>
+__global__ __launch_bounds__(kLdsWpb * 64) void attn_prefix_bwd_lds(int G, int P, int R, int ntiles,
                                                            const int* __restrict__ tiles,
                                                            const int* __restrict__ row_first, int H,
                                                            int nchunk, int uc, const T* __restrict__ qkv,
@@ -618,15 +527,15 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_bwd_lds(int G, int P, in
   static_assert(sizeof(T) == 2, "MFMA attention backward: 16-bit operands");
   constexpr int SLOT = 4 * 2048 + 2 * 256;  // q | k | v | dO tiles, row_first, lse
   constexpr int PER = 10;
-  __shared__ CLIPK_LDS_ALIGN char sm[WPB][NS * SLOT + 16 * TRS * 2];
+  __shared__ CLIPK_LDS_ALIGN char sm[kLdsWpb][kLdsSlots * SLOT + 16 * TRS * 2];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r16 = lane & 15, g4 = lane >> 4;
-  const int wid = blockIdx.x * WPB + w;
+  const int wid = blockIdx.x * kLdsWpb + w;
   if (wid >= G * nchunk * H) return;  // wave-uniform
   const int h = wid % H, k = (wid / H) % nchunk, g = wid / (H * nchunk);
   const int W = H * 64;
   char* ring = sm[w];
-  short* tKp = reinterpret_cast<short*>(ring + NS * SLOT);
+  short* tKp = reinterpret_cast<short*>(ring + kLdsSlots * SLOT);
   const int gR = g * R;
   const T* qh = qkv + h * 64;
   const int u_begin = k * uc, u_end = min((k + 1) * uc, ntiles + 1);
@@ -660,17 +569,17 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_bwd_lds(int G, int P, in
   }
   const int nu = u_end - u_begin;
 #pragma unroll
-  for (int d = 0; d < NS - 1; ++d)
+  for (int d = 0; d < kLdsSlots - 1; ++d)
     if (d < nu) issue(u_begin + d, d);
   for (int i = 0; i < nu; ++i) {
     const int u = u_begin + i;
     lds_fence();
-    if (i + NS - 1 < nu) issue(u + NS - 1, (i + NS - 1) % NS);
-    const int ahead = min(NS - 1, nu - 1 - i);
-    if (ahead >= 2) vm_wait<2 * PER>();
-    else if (ahead == 1) vm_wait<PER>();
+    if (i + kLdsSlots - 1 < nu) issue(u + kLdsSlots - 1, (i + kLdsSlots - 1) % kLdsSlots);
+    static_assert(kLdsSlots == 2, "the wait below: at most one tile issued after tile i");
+    const int ahead = min(kLdsSlots - 1, nu - 1 - i);  // tiles issued after tile i
+    if (ahead == 1) vm_wait<PER>();
     else vm_wait<0>();
-    const char* b = ring + (i % NS) * SLOT;
+    const char* b = ring + (i % kLdsSlots) * SLOT;
     const char* tQ = b;
     const char* tKo = b + 2048;
     const char* tD = b + 3 * 2048;
@@ -690,53 +599,16 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_bwd_lds(int G, int P, in
     }
     const float l2 = sL[r16];
     const int first2 = own_is_prefix ? 0 : sF[r16] - t0;
+    float l1[4];
+    int first1[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      l1[r] = sL[4 * g4 + r];
+      first1[r] = own_is_prefix ? 0 : sF[4 * g4 + r] - t0;
+    }
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    f32x4 s1p = z, s2p = z, p1p = z, p2p = z, s1o = z, s2o = z, p1o = z, p2o = z;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      s1p = mfma32_t<T>(q[kk], kp[kk], s1p);
-      s2p = mfma32_t<T>(kp[kk], q[kk], s2p);
-      p1p = mfma32_t<T>(d[kk], vp[kk], p1p);
-      p2p = mfma32_t<T>(vp[kk], d[kk], p2p);
-      s1o = mfma32_t<T>(q[kk], ko[kk], s1o);
-      s2o = mfma32_t<T>(ko[kk], q[kk], s2o);
-      p1o = mfma32_t<T>(d[kk], vo[kk], p1o);
-      p2o = mfma32_t<T>(vo[kk], d[kk], p2o);
-    }
-    float P2p[4], P2o[4], Dsum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int j = 4 * g4 + r;
-      P2p[r] = (qok && j < pre) ? __expf(s2p[r] * kScale - l2) : 0.f;
-      P2o[r] = (qok && j <= r16 && j >= first2) ? __expf(s2o[r] * kScale - l2) : 0.f;
-      Dsum += P2p[r] * p2p[r] + P2o[r] * p2o[r];
-    }
-    Dsum = xsum4(Dsum);
-    float dS2p[4], dS2o[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      dS2p[r] = P2p[r] * (p2p[r] - Dsum);
-      dS2o[r] = P2o[r] * (p2o[r] - Dsum);
-    }
-    float P1p[4], P1o[4], dS1p[4], dS1o[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i4 = 4 * g4 + r;
-      const bool iok = i4 < n;
-      const float Di = __shfl(Dsum, i4, 64);
-      const float l1 = sL[i4];
-      const int first1 = own_is_prefix ? 0 : sF[i4] - t0;
-      P1p[r] = (iok && r16 < pre) ? __expf(s1p[r] * kScale - l1) : 0.f;
-      P1o[r] = (iok && r16 <= i4 && r16 >= first1) ? __expf(s1o[r] * kScale - l1) : 0.f;
-      dS1p[r] = P1p[r] * (p1p[r] - Di);
-      dS1o[r] = P1o[r] * (p1o[r] - Di);
-    }
-    const s16x4 bPp = pack4<T>(P1p[0], P1p[1], P1p[2], P1p[3]);
-    const s16x4 bSp = pack4<T>(dS1p[0], dS1p[1], dS1p[2], dS1p[3]);
-    const s16x4 bPo = pack4<T>(P1o[0], P1o[1], P1o[2], P1o[3]);
-    const s16x4 bSo = pack4<T>(dS1o[0], dS1o[1], dS1o[2], dS1o[3]);
-    const s16x4 bTp = pack4<T>(dS2p[0], dS2p[1], dS2p[2], dS2p[3]);
-    const s16x4 bTo = pack4<T>(dS2o[0], dS2o[1], dS2o[2], dS2o[3]);
+    s16x4 bPp, bSp, bPo, bSo, bTp, bTo;
+    bwd_tile_operands<T>(q, ko, vo, d, kp, vp, l2, l1, first2, first1, n, pre, r16, g4, bPp, bSp, bPo, bSo, bTp, bTo);
     T* orow = dqkv + (gR + t0 + r16) * lddq + h * 64;
     f32x4 acc[4];
     s16x4 ta[4], tb[4];
@@ -767,33 +639,21 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_bwd_lds(int G, int P, in
     }
     if (!own_is_prefix) store_tile64<T>(orow + 2 * W, acc, 1.0f, qok);  // dV
   }
-  float* pb = part + ((size_t)g * nchunk + k) * 16 * (2 * W);
-  if (r16 < P) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      float* dst = pb + (size_t)r16 * 2 * W + h * 64 + 16 * t + 4 * g4;
-      *reinterpret_cast<f32x4*>(dst) = dkp[t] * kScale;
-      *reinterpret_cast<f32x4*>(dst + W) = dvp[t];
-    }
-  }
+  store_prefix_partials(part + ((size_t)g * nchunk + k) * 16 * (2 * W), W, h, P, r16, g4, dkp, dvp);
 }
 
 // ------------------------------------------------------------------ fp32 kernels (PREC fp32; fp32 calls
 // without CLIPK_PREFIX_SPLIT -- PREC fp32s runs attn_prefix_*_split below)
-// One wave per (group, chunk of f32_uc units, head); blocks of WPB waves (f32_wpb) share one
+// One wave per (group, chunk of f32_uc units, head); blocks of kF32Wpb waves share one
 // (group, head), so the prefix K/V rows are staged into LDS once per block. Lane = 4 r + s: row
 // r of the unit (query in the forward and for dQ, key for dK / dV) and 16-column slice s of
 // the head; a dot product is 16 FMAs on the lane's slice plus a quad sum (2 DPP adds). K/V
 // (and, for the backward's key phases, Q / dO) rows are read from LDS, where the 16 lanes of
 // one slice read the same 64 B (a broadcast). All arithmetic fp32, the reference's
 // nn.MultiheadAttention math (model.py:183), exact softmax (online max / rescale, fwd).
-// waves per block (template WPB; knob CLIPK_F32ATTN_WPB: 2 (default), 4 or 8). fp32s headline
-// (profiles/r04h/): backward 2.86 -> 2.76 ms/step at 2 vs 4, forward equal, 8 no better
-static int f32_wpb() { static int c = chunk_env("CLIPK_F32ATTN_WPB", 2); return c == 4 || c == 8 ? c : 2; }
-
-// a wave's own LDS writes visible to its other lanes (program order on the LDS; no reordering
-// by the compiler across this point)
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// waves per block: 2. fp32s headline (profiles/r04h/): backward 2.86 -> 2.76 ms/step at 2 against
+// 4, forward equal, 8 no better
+constexpr int kF32Wpb = 2;
 
 // unit u of group-relative tiles: first row t0, rows n (<= 16), prefix keys pre, and for row rr
 // the first row of its class (causal block-diagonal mask inside the tile)
@@ -810,25 +670,23 @@ __device__ __forceinline__ void f32_unit(const int* __restrict__ tiles, const in
   first = u == 0 ? 0 : row_first[t0 + rr] - t0;
 }
 
-// block (g, h, chunk block kb): waves take chunks kb * WPB + w; stages the prefix K / V rows
+// block (g, h, chunk block kb): waves take chunks kb * kF32Wpb + w; stages the prefix K / V rows
 // of (g, h) (P <= 16 rows x 64 fp32) into sKp / sVp. These sit in DYNAMIC LDS sized to P rows
 // (2 x P x 256 B, f32_prefix_lds): at the CoCoOp P of 5 a block takes 2.5 KiB for them instead of
 // 8, which lets 5 backward blocks (10 waves) and 8 forward blocks (16 waves) share a CU instead
 // of 4 and 6 (LDS was the occupancy limit: 34 / 24 KiB per 2-wave block)
-template <int WPB>
 __device__ __forceinline__ void f32_block(int H, int nchunk, int& g, int& h, int& k, int& w) {
-  const int nkb = (nchunk + WPB - 1) / WPB;
+  const int nkb = (nchunk + kF32Wpb - 1) / kF32Wpb;
   const int b = blockIdx.x;
   h = b % H;
   const int kb = (b / H) % nkb;
   g = b / (H * nkb);
   w = threadIdx.x >> 6;
-  k = kb * WPB + w;
+  k = kb * kF32Wpb + w;
 }
-template <int WPB>
 __device__ __forceinline__ void f32_stage_prefix(const float* __restrict__ qkv, size_t row0, int P, int ldq, int col,
                                                  int W, float* sKp, float* sVp) {
-  for (int i = threadIdx.x; i < P * 16; i += WPB * 64) {  // P rows x 16 float4
+  for (int i = threadIdx.x; i < P * 16; i += kF32Wpb * 64) {  // P rows x 16 float4
     const int j = i >> 4, c = i & 15;
     const float* b = qkv + (row0 + j) * ldq + col + 4 * c;
     reinterpret_cast<f32x4*>(sKp)[i] = *reinterpret_cast<const f32x4*>(b + W);
@@ -837,19 +695,18 @@ __device__ __forceinline__ void f32_stage_prefix(const float* __restrict__ qkv, 
 }
 static size_t f32_prefix_lds(int P) { return (size_t)2 * P * 64 * sizeof(float); }
 
-template <int WPB>
-__global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_f32(
+__global__ __launch_bounds__(kF32Wpb * 64) void attn_prefix_fwd_f32(
     int G, int P, int R, int ntiles, const int* __restrict__ tiles, const int* __restrict__ row_first, int H,
     int nchunk, int uc, const float* __restrict__ qkv, int ldq, float* __restrict__ out, int ldo,
     float* __restrict__ lse, int cls0) {
   extern __shared__ CLIPK_LDS_ALIGN float sPre[];  // prefix K | V rows, P x 64 each (f32_prefix_lds)
   float* const sKp = sPre;
   float* const sVp = sPre + P * 64;
-  __shared__ CLIPK_LDS_ALIGN float sK[WPB][16 * 64], sV[WPB][16 * 64];
+  __shared__ CLIPK_LDS_ALIGN float sK[kF32Wpb][16 * 64], sV[kF32Wpb][16 * 64];
   int g, h, k, w;
-  f32_block<WPB>(H, nchunk, g, h, k, w);
+  f32_block(H, nchunk, g, h, k, w);
   const int W = H * 64;
-  f32_stage_prefix<WPB>(qkv, (size_t)g * R, P, ldq, h * 64, W, sKp, sVp);
+  f32_stage_prefix(qkv, (size_t)g * R, P, ldq, h * 64, W, sKp, sVp);
   __syncthreads();
   if (k >= nchunk) return;  // wave-uniform; no block barrier follows
   const int lane = threadIdx.x & 63, r = lane >> 2, s = lane & 3;
@@ -876,7 +733,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_f32(
     for (int d = 0; d < 16; ++d) q[d] = qn[d] * kScale;
     st16x(sk + r * 64 + kSl * s, kn);
     st16x(sv + r * 64 + kSl * s, vn);
-    lds_sync();
+    lds_fence();
     if (u + 1 < u_end) fetch(u + 1);
     // exact two-pass softmax over the prefix keys, then the row's own class keys first..rr: the
     // scores stay in registers (key loops unrolled to 16 with wave-uniform bounds), so there is
@@ -933,7 +790,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_f32(
       st16x(out + row * ldo + h * 64 + kSl * s, o);
       if (lse && s == 0) lse[row * H + h] = m + __logf(l);
     }
-    lds_sync();  // this unit's sK / sV reads done before the next unit's writes (program order)
+    lds_fence();  // this unit's sK / sV reads done before the next unit's writes (program order)
   }
 }
 
@@ -944,8 +801,8 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_f32(
 // the chunk in registers and written once per chunk (prefix_kv_reduce sums the chunks).
 // OS (grad dtype CLIPK_F32S): dQ / dK / dV stored in the pre-split form of the qkv input-grad
 // GEMM's A (st16x_split; the prefix rows' dK / dV by prefix_kv_reduce_split), the same bytes
-template <int WPB, bool OS = false>
-__global__ __launch_bounds__(WPB * 64, 2) void attn_prefix_bwd_f32(  // >= 2 waves per SIMD (<= 256 VGPRs)
+template <bool OS = false>
+__global__ __launch_bounds__(kF32Wpb * 64, 2) void attn_prefix_bwd_f32(  // >= 2 waves per SIMD (<= 256 VGPRs)
     int G, int P, int R, int ntiles, const int* __restrict__ tiles, const int* __restrict__ row_first, int H,
     int nchunk, int uc, const float* __restrict__ qkv, int ldq, const float* __restrict__ o_fwd, int ldof,
     const float* __restrict__ dout, int lddo, const float* __restrict__ lse, float* __restrict__ dqkv, int lddq,
@@ -956,12 +813,12 @@ __global__ __launch_bounds__(WPB * 64, 2) void attn_prefix_bwd_f32(  // >= 2 wav
   // padded rows (bank-conflict-free stores): K|V then Q|dO rows at stride RS floats; P / dS at
   // stride PS (a column of 16 query rows written by one lane per row hit 2 banks at stride 32)
   constexpr int RS = 68, PS = 33;
-  __shared__ CLIPK_LDS_ALIGN float sA[WPB][16 * RS], sB[WPB][16 * RS];
-  __shared__ CLIPK_LDS_ALIGN float sP[WPB][16 * PS], sS[WPB][16 * PS];
+  __shared__ CLIPK_LDS_ALIGN float sA[kF32Wpb][16 * RS], sB[kF32Wpb][16 * RS];
+  __shared__ CLIPK_LDS_ALIGN float sP[kF32Wpb][16 * PS], sS[kF32Wpb][16 * PS];
   int g, h, k, w;
-  f32_block<WPB>(H, nchunk, g, h, k, w);
+  f32_block(H, nchunk, g, h, k, w);
   const int W = H * 64;
-  f32_stage_prefix<WPB>(qkv, (size_t)g * R, P, ldq, h * 64, W, sKp, sVp);
+  f32_stage_prefix(qkv, (size_t)g * R, P, ldq, h * 64, W, sKp, sVp);
   __syncthreads();
   if (k >= nchunk) return;
   const int lane = threadIdx.x & 63, r = lane >> 2, s = lane & 3;
@@ -1003,7 +860,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void attn_prefix_bwd_f32(  // >= 2 wav
     const float li = lin;
     st16x(sa + r * RS + kSl * s, kn);
     st16x(sb + r * RS + kSl * s, vn);
-    lds_sync();
+    lds_fence();
     if (u + 1 < u_end) fetch(u + 1);
     // phase 1: lane = query row rr
     float dq[16];
@@ -1036,7 +893,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void attn_prefix_bwd_f32(  // >= 2 wav
     // reads of K / V: program order)
     st16x(sa + r * RS + kSl * s, q);
     st16x(sb + r * RS + kSl * s, dO);
-    lds_sync();
+    lds_fence();
     // phases 2 / 3: lane = key; sum over the unit's queries i of dS[i][key] q_i, P[i][key] dO_i
     auto keysum = [&](int col, float* dk, float* dv) {
       for (int i = 0; i < n; ++i) {
@@ -1083,7 +940,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void attn_prefix_bwd_f32(  // >= 2 wav
         }
       }
     }
-    lds_sync();
+    lds_fence();
   }
   if (r < P) {
     // (dK = sum dS q with q already scaled: no further factor)
@@ -1257,7 +1114,7 @@ __global__ __launch_bounds__(WPB * 64) void attn_prefix_fwd_split(
     split_pack4(eo[0] * kPScale, eo[1] * kPScale, eo[2] * kPScale, eo[3] * kPScale, boH, boL);
     const float inv = kPInv / ps;
     lds_fence();
-    // O^T = V^T P^T (see attn_prefix_fwd_mfma): lane (r16, g4) gets O[query r16][16 t + 4 g4 .. + 3]
+    // O^T = V^T P^T (see attn_prefix_fwd_lds): lane (r16, g4) gets O[query r16][16 t + 4 g4 .. + 3]
     float* orow = out + (gR + t0 + r16) * ldo + h * 64;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -1511,48 +1368,14 @@ static int prefix_fwd(int G, int P, int R, int ntiles, const int* tiles, const i
     const int uc = fwd_chunk();
     const int nchunk = n_chunks(ntiles, uc);
     const long waves = (long)G * nchunk * H;
-    if (const int ns = lds_slots()) {
-      const int wpb = lds_wpb();
-      auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((waves + wpb - 1) / wpb), dim3(64 * wpb), 0, st, G, P, R, ntiles, tiles,
-                           row_first, H, nchunk, uc, (const T*)qkv, ldq, (T*)out, ldo, lse, cls0);
-      };
-#define CLIPK_LDS_GO(K, T_, ...)                                                               \
-  if (ns == 2) { if (wpb == 1) go(K<T_, 2, 1 __VA_ARGS__>); else if (wpb == 2) go(K<T_, 2, 2 __VA_ARGS__>); \
-                 else go(K<T_, 2, 4 __VA_ARGS__>); }                                                 \
-  else { if (wpb == 1) go(K<T_, 3, 1 __VA_ARGS__>); else if (wpb == 2) go(K<T_, 3, 2 __VA_ARGS__>);     \
-         else go(K<T_, 3, 4 __VA_ARGS__>); }
-      CLIPK_LDS_GO(attn_prefix_fwd_lds, T)
-      CLIPK_CHECK_LAUNCH();
-      return CLIPK_OK;
-    }
-    const int b = fwd_batch();
-    const int wpb = prefix_wpb();
-    auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3((waves + wpb - 1) / wpb), dim3(64 * wpb), 0, st, G, P, R, ntiles, tiles,
-                         row_first, H, nchunk, uc, (const T*)qkv, ldq, (T*)out, ldo, lse, cls0);
-    };
-    if (wpb == 8) {
-      if (b == 1) go(attn_prefix_fwd_mfma<T, 1, 8>);
-      else if (b == 2) go(attn_prefix_fwd_mfma<T, 2, 8>);
-      else go(attn_prefix_fwd_mfma<T, 4, 8>);
-    } else {
-      if (b == 1) go(attn_prefix_fwd_mfma<T, 1>);
-      else if (b == 2) go(attn_prefix_fwd_mfma<T, 2>);
-      else go(attn_prefix_fwd_mfma<T, 4>);
-    }
+    hipLaunchKernelGGL(attn_prefix_fwd_lds<T>, dim3((waves + kLdsWpb - 1) / kLdsWpb), dim3(64 * kLdsWpb), 0, st, G, P,
+                       R, ntiles, tiles, row_first, H, nchunk, uc, (const T*)qkv, ldq, (T*)out, ldo, lse, cls0);
   } else {
     const int uc = f32_uc(G, ntiles, H, kF32FwdWpc);
     const int nchunk = n_chunks(ntiles, uc);
-    auto go = [&](auto kern, int wpb) {
-      const long blocks = (long)G * ((nchunk + wpb - 1) / wpb) * H;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * wpb), f32_prefix_lds(P), st, G, P, R, ntiles, tiles, row_first,
-                         H, nchunk, uc, (const float*)qkv, ldq, (float*)out, ldo, lse, cls0);
-    };
-    const int wpb = f32_wpb();
-    if (wpb == 2) go(attn_prefix_fwd_f32<2>, 2);
-    else if (wpb == 8) go(attn_prefix_fwd_f32<8>, 8);
-    else go(attn_prefix_fwd_f32<4>, 4);
+    const long blocks = (long)G * ((nchunk + kF32Wpb - 1) / kF32Wpb) * H;
+    hipLaunchKernelGGL(attn_prefix_fwd_f32, dim3(blocks), dim3(64 * kF32Wpb), f32_prefix_lds(P), st, G, P, R, ntiles,
+                       tiles, row_first, H, nchunk, uc, (const float*)qkv, ldq, (float*)out, ldo, lse, cls0);
   }
   CLIPK_CHECK_LAUNCH();
   return CLIPK_OK;
@@ -1566,50 +1389,22 @@ static int prefix_bwd(int G, int P, int R, int ntiles, const int* tiles, const i
   constexpr bool mfma = sizeof(TG) == 2 && sizeof(T) == 2;
   const int uc = mfma ? bwd_uc(G, ntiles, H) : f32_uc(G, ntiles, H, kF32BwdWpc);
   const int nchunk = n_chunks(ntiles, uc);
-  const long waves = (long)G * nchunk * H;
-  if constexpr (mfma && __is_same(T, TG)) {
-    if (const int ns = lds_slots()) {
-      const int wpb = lds_wpb();
-      auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((waves + wpb - 1) / wpb), dim3(64 * wpb), 0, st, G, P, R, ntiles, tiles,
-                           row_first, H, nchunk, uc, (const T*)qkv, ldq, (const T*)dout, lddo, lse, (T*)dqkv,
-                           lddq, part, cls0);
-      };
-      CLIPK_LDS_GO(attn_prefix_bwd_lds, T)
-      CLIPK_CHECK_LAUNCH();
-      const int W = H * 64;
-      hipLaunchKernelGGL((prefix_kv_reduce<TG>), dim3(G * P, (2 * W + 255) / 256), dim3(256), 0, st, P, R, W,
-                         nchunk, part, (TG*)dqkv, lddq);
-      CLIPK_CHECK_LAUNCH();
-      return CLIPK_OK;
-    }
-  }
   if constexpr (mfma) {
-    const int wpb = prefix_wpb();
-    auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3((waves + wpb - 1) / wpb), dim3(64 * wpb), 0, st, G, P, R, ntiles, tiles,
-                         row_first, H, nchunk, uc, (const T*)qkv, ldq, (const TG*)dout, lddo, lse, (TG*)dqkv,
-                         lddq, part, cls0);
-    };
-    if (wpb == 8) {
-      if (bwd_batch() == 1) go(attn_prefix_bwd_mfma<T, TG, 1, 8>);
-      else go(attn_prefix_bwd_mfma<T, TG, 2, 8>);
-    } else {
-      if (bwd_batch() == 1) go(attn_prefix_bwd_mfma<T, TG, 1>);
-      else go(attn_prefix_bwd_mfma<T, TG, 2>);
-    }
+    const long waves = (long)G * nchunk * H;
+    if constexpr (__is_same(T, TG))
+      hipLaunchKernelGGL(attn_prefix_bwd_lds<T>, dim3((waves + kLdsWpb - 1) / kLdsWpb), dim3(64 * kLdsWpb), 0, st, G,
+                         P, R, ntiles, tiles, row_first, H, nchunk, uc, (const T*)qkv, ldq, (const T*)dout, lddo, lse,
+                         (T*)dqkv, lddq, part, cls0);
+    else  // operand dtype != gradient dtype: the register-operand kernel converts as it loads
+      hipLaunchKernelGGL((attn_prefix_bwd_mfma<T, TG>), dim3((waves + kRegWpb - 1) / kRegWpb), dim3(64 * kRegWpb), 0,
+                         st, G, P, R, ntiles, tiles, row_first, H, nchunk, uc, (const T*)qkv, ldq, (const TG*)dout,
+                         lddo, lse, (TG*)dqkv, lddq, part, cls0);
   } else {
     static_assert(mfma || (sizeof(T) == 4 && sizeof(TG) == 4), "fp32 backward");
-    auto go = [&](auto kern, int wpb) {
-      const long blocks = (long)G * ((nchunk + wpb - 1) / wpb) * H;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * wpb), f32_prefix_lds(P), st, G, P, R, ntiles, tiles, row_first,
-                         H, nchunk, uc, (const float*)qkv, ldq, (const float*)ofwd, ldof, (const float*)dout, lddo,
-                         lse, (float*)dqkv, lddq, part, cls0);
-    };
-    const int wpb = f32_wpb();
-    if (wpb == 2) go(attn_prefix_bwd_f32<2, OS>, 2);
-    else if (wpb == 8) go(attn_prefix_bwd_f32<8, OS>, 8);
-    else go(attn_prefix_bwd_f32<4, OS>, 4);
+    const long blocks = (long)G * ((nchunk + kF32Wpb - 1) / kF32Wpb) * H;
+    hipLaunchKernelGGL(attn_prefix_bwd_f32<OS>, dim3(blocks), dim3(64 * kF32Wpb), f32_prefix_lds(P), st, G, P, R,
+                       ntiles, tiles, row_first, H, nchunk, uc, (const float*)qkv, ldq, (const float*)ofwd, ldof,
+                       (const float*)dout, lddo, lse, (float*)dqkv, lddq, part, cls0);
   }
   CLIPK_CHECK_LAUNCH();
   const int W = H * 64;

@@ -30,7 +30,10 @@ __device__ __forceinline__ void load_cols8(const T* p, float* out) {
   for (int c = 0; c < 8 / V; ++c) load16_f32<T>(p + c * V, out + c * V);
 }
 
-__device__ __forceinline__ void lds_fence_a() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// A wave's LDS accesses issued so far are complete: its own writes are visible to its other
+// lanes and its reads have returned (program order on the LDS), and the compiler moves no memory
+// access across this point. Wave-private tiles need no block barrier.
+__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 __device__ __forceinline__ float dot64(const float* a, const float* b) {
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;

@@ -766,14 +766,13 @@ def test_attention_prefix_cls_group0(dev, dtype, gdtype, G, C, P, H, max_q):
 
 
 @pytest.mark.parametrize("knobs", [
-    {"CLIPK_PREFIX_LDS": "0"},
-    {"CLIPK_PREFIX_LDS": "3", "CLIPK_PREFIX_LDS_WPB": "1"},
-    {"CLIPK_PREFIX_LDS": "2", "CLIPK_PREFIX_LDS_WPB": "2", "CLIPK_PREFIX_FWD_CHUNK": "1",
-     "CLIPK_PREFIX_BWD_CHUNK": "3"},
-])
+    {"CLIPK_PREFIX_FWD_CHUNK": "1", "CLIPK_PREFIX_BWD_CHUNK": "3"},
+    # an odd ring wrap, and a chunk size that divides none of the tile counts
+    {"CLIPK_PREFIX_FWD_CHUNK": "3", "CLIPK_PREFIX_BWD_CHUNK": "5"},
+], ids=["chunk_1_3", "chunk_3_5"])
 def test_attention_prefix_kernel_variants(knobs):
-    """The other shared-prefix attention variants -- the register-operand kernels, a 3-slot
-    LDS ring, 1- and 2-wave blocks, 1- and 3-tile chunks -- through the same cases, in a child
+    """Other chunkings of the shared-prefix attention -- 1-, 3- and 5-tile chunks, where the LDS
+    ring's wrap and the per-chunk partials can go wrong -- through the same cases, in a child
     process (the knobs are read once per process)."""
     env = dict(os.environ, **knobs)
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider", os.path.abspath(__file__),

@@ -1,10 +1,11 @@
 """Shared-prefix attention fwd / bwd at the bench shape (CoCoOp ViT-B/16 text, G = 8 images,
-C = 1000 classes, P = 5), timed with HIP events on the launch stream; one process per knob
-setting (the CLIPK_PREFIX_* knobs are read once per process).
+C = 1000 classes, P = 5), timed with HIP events on the launch stream; one process per setting
+(the CLIPK_PREFIX_*_CHUNK knobs are read once per process).
 
     python tools/attn_sweep.py            # sweep (spawns one child per setting)
     python tools/attn_sweep.py --one      # time the current environment's setting
-                                          # (SWEEP_DTYPE=fp16 | fp32 | fp32s, SWEEP_CACHE)
+                                          # (SWEEP_DTYPE=fp16 | fp32 | fp32s, SWEEP_GRAD=bf16,
+                                          # SWEEP_CACHE=clean | warm | dirty)
     python tools/attn_sweep.py --anyl     # the fp32 any-L forward (attn_fwd_f32): ViT-B/16
                                           # L = 197 (100 images) and plain text L = 77 (causal)
 """
@@ -40,9 +41,13 @@ def one(iters=30):
     f32, split = sdt in ("fp32", "fp32s"), sdt == "fp32s"
     flags = N.PREFIX_SPLIT if split else 0
     dt, did, esz = (torch.float32, N.F32, 4) if f32 else (torch.float16, N.F16, 2)
+    # SWEEP_GRAD=bf16 (with fp16 operands): the mixed backward, attn_prefix_bwd_mfma
+    gdt, gid = dt, did
+    if os.environ.get("SWEEP_GRAD") == "bf16" and not f32:
+        gdt, gid = torch.bfloat16, N.BF16
     qkv = (torch.randn(G * R, 3 * W, device=dev) * 0.5).to(dt)
-    dout = (torch.randn(G * R, W, device=dev) * 0.5).to(dt)
-    dq = torch.empty(G * R, 3 * W, device=dev, dtype=dt)
+    dout = (torch.randn(G * R, W, device=dev) * 0.5).to(gdt)
+    dq = torch.empty(G * R, 3 * W, device=dev, dtype=gdt)
     nb = N.load().clipk_attention_prefix_ws_bytes(G, nt, H)
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
     # clean-cache flush: READ 1 GiB (a write flush would leave the 256-MB Infinity Cache full
@@ -55,7 +60,7 @@ def one(iters=30):
     o, lse = ops.attention_prefix(qkv, G, P, R, tiles, row_first, H, lse=True, flags=flags)
 
     def bwd():
-        N.call("clipk_attention_prefix_bwd_ex", did, did, G, P, R, nt, p(tiles), p(row_first), H, p(qkv),
+        N.call("clipk_attention_prefix_bwd_ex", did, gid, G, P, R, nt, p(tiles), p(row_first), H, p(qkv),
                3 * W, p(o), W, p(dout), W, p(lse), p(dq), 3 * W, p(ws), nb, flags, sp)
 
     def fwd():
@@ -86,16 +91,10 @@ def one(iters=30):
 
 
 SWEEP = [
-    {"CLIPK_PREFIX_LDS": "0"},
-    {"CLIPK_PREFIX_LDS": "0", "CLIPK_PREFIX_WPB": "8"},
     {},
-    {"CLIPK_PREFIX_LDS_WPB": "4"},
-    {"CLIPK_PREFIX_LDS": "3", "CLIPK_PREFIX_LDS_WPB": "4"},
-    {"CLIPK_PREFIX_LDS_WPB": "4", "CLIPK_PREFIX_FWD_CHUNK": "4", "CLIPK_PREFIX_BWD_CHUNK": "8"},
-    {"CLIPK_PREFIX_LDS": "0", "SWEEP_CACHE": "warm"},
-    {"CLIPK_PREFIX_LDS_WPB": "4", "SWEEP_CACHE": "warm"},
-    {"CLIPK_PREFIX_LDS": "0", "SWEEP_CACHE": "dirty"},
-    {"CLIPK_PREFIX_LDS_WPB": "4", "SWEEP_CACHE": "dirty"},
+    {"CLIPK_PREFIX_FWD_CHUNK": "4", "CLIPK_PREFIX_BWD_CHUNK": "8"},
+    {"SWEEP_CACHE": "warm"},
+    {"SWEEP_CACHE": "dirty"},
 ]
 
 
