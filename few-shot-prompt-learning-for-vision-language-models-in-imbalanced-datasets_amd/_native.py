@@ -51,6 +51,7 @@ ADAM_ADAM, ADAM_ADAMW, ADAM_AMSGRAD = 0, 1, 2  # clipk_adam_step_multi modes
 COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE, COLOR_GRAYSCALE = 1, 2, 3, 4, 5
 COLOR_MAX_OPS, COLOR_DESC = 5, 12
 COLORBLUR_DESC, BLUR_MAX_RADIUS = 16, 7  # clipk_image_color_blur: descriptor width, largest box radius
+RESAMPLE_PARAMS = 12  # clipk_resample_tables: int64 words per image record
 CONV_RES, CONV_RELU, CONV_OUT_F32 = 1, 2, 4  # clipk_conv2d_nhwc flags
 PROF_NONE, PROF_GEMM_FC, PROF_GEMM_ALL, PROF_ATTN, PROF_LN, PROF_GEMM_DGELU = 0, 1, 2, 3, 4, 5
 
@@ -85,6 +86,9 @@ SIGNATURES = {
     "clipk_gemm_ln_gamma": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     "clipk_gemm_ln_merge": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "clipk_image_resample": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "clipk_image_resample_at": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "clipk_resample_tables": (_I, [_I, _I, _P, _P, _P]),
+    "clipk_resample_tables_host": (_I, [_I, _I, _P, _P, _P]),
     "clipk_image_color": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
     "clipk_image_color_blur": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
     "clipk_gemm_stamps": (_I, [_P, _S]),

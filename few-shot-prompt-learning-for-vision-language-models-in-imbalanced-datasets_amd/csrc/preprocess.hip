@@ -9,16 +9,19 @@
 // transforms.py:206-354: Resize + CenterCrop for test, RandomResizedCrop + flip for train)
 // that run per image on the host. The coefficient tables (Pillow libImaging/Resample.c
 // precompute_coeffs + normalize_coeffs_8bpc) are built on the host in float64
-// (fsp_amd/data/preprocess.py); these kernels do the integer work. HBM/latency-bound: each
-// output pixel reads ~ksize source pixels per pass.
+// (fsp_amd/data/preprocess.py), or on the device by resample_tables_kernel (clipk_resample_tables;
+// arithmetic in resample_ops.h, the same integers); these kernels do the integer work.
+// HBM/latency-bound: each output pixel reads ~ksize source pixels per pass.
+// clipk_image_resample_at: the same kernels on images addressed absolutely (an image bank).
 #include <string.h>
 
 #include "common.h"
 #include "color_ops.h"
+#include "resample_ops.h"
 
 namespace clipk {
 
-constexpr int kPrecBits = 22;  // Pillow PRECISION_BITS = 32 - 8 - 2
+constexpr int kPrecBits = resample::kPrecisionBits;  // Pillow PRECISION_BITS: one constant for the tables and the kernels
 
 __device__ __forceinline__ int clip8(int s) {
   const int v = s >> kPrecBits;  // arithmetic shift, as Pillow's lookup index
@@ -89,6 +92,26 @@ __global__ __launch_bounds__(256) void resample_v_kernel(int B, int S, const lon
       ((float*)out)[oi] = (f - mean[c]) / stdv[c];  // Normalize: sub_(mean).div_(std)
     }
   }
+}
+
+// ---- coefficient tables (clipk_resample_tables) ----------------------------------------------
+// One thread per table row: B images x (S h rows, then S v rows). A row's sum runs over its taps
+// in tap order inside the thread (no reduction across lanes: the order is part of the result),
+// and its taps are looped over, never held in registers (ksize has no bound). Every write lies in
+// the row's own 2 + ksize ints at the offset and stride the host laid out.
+// params (int64 x CLIPK_RESAMPLE_PARAMS per image): include/clipk.h.
+__global__ __launch_bounds__(256) void resample_tables_kernel(int B, int S, const long long* __restrict__ params,
+                                                              int* __restrict__ tab) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)B * 2 * S) return;
+  const int b = (int)(i / (2 * S));
+  const int v = (int)((i / S) & 1), r = (int)(i % S);
+  const long long* p = params + (size_t)b * CLIPK_RESAMPLE_PARAMS + (v ? 5 : 0);
+  if (r >= (int)params[(size_t)b * CLIPK_RESAMPLE_PARAMS + 10]) return;
+  const int ks = (int)p[4];
+  const resample::Axis a = resample::make_axis((int)p[0], (int)p[1]);
+  const int rel = v ? (int)params[(size_t)b * CLIPK_RESAMPLE_PARAMS + 11] : 0;
+  resample::table_row(a, (int)p[2] + r, rel, ks, tab + p[3] + (size_t)r * (2 + ks));
 }
 
 // ---- colour stage (clipk_image_color) -------------------------------------------------------
@@ -255,10 +278,12 @@ __global__ __launch_bounds__(kColorThreads) void color_kernel(int S, uint8_t* __
 
 using namespace clipk;
 
-extern "C" int clipk_image_resample(int B, int S, int rows_max, const void* src, const long long* desc,
-                                    const int* tables, void* tmp, const float* mean, const float* stdv,
-                                    int out_uint8, void* out, void* stream) {
-  if (!src || !desc || !tables || !tmp || !out || (!out_uint8 && (!mean || !stdv))) return CLIPK_EINVAL;
+// src + desc[0] is an image's first byte: the packed upload and its offsets (clipk_image_resample),
+// or null and absolute addresses (clipk_image_resample_at).
+static int resample_launch(int B, int S, int rows_max, const void* src, const long long* desc, const int* tables,
+                           void* tmp, const float* mean, const float* stdv, int out_uint8, void* out,
+                           void* stream) {
+  if (!desc || !tables || !tmp || !out || (!out_uint8 && (!mean || !stdv))) return CLIPK_EINVAL;
   if (B < 0 || S <= 0 || rows_max <= 0) return CLIPK_ESHAPE;
   if (B == 0) return CLIPK_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -273,6 +298,59 @@ extern "C" int clipk_image_resample(int B, int S, int rows_max, const void* src,
     hipLaunchKernelGGL(resample_v_kernel<false>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, B, S, desc,
                        tables, (const uint8_t*)tmp, mean, stdv, out);
   CLIPK_CHECK_LAUNCH();
+  return CLIPK_OK;
+}
+
+extern "C" int clipk_image_resample(int B, int S, int rows_max, const void* src, const long long* desc,
+                                    const int* tables, void* tmp, const float* mean, const float* stdv,
+                                    int out_uint8, void* out, void* stream) {
+  if (!src) return CLIPK_EINVAL;
+  return resample_launch(B, S, rows_max, src, desc, tables, tmp, mean, stdv, out_uint8, out, stream);
+}
+
+extern "C" int clipk_image_resample_at(int B, int S, int rows_max, const long long* desc, const int* tables,
+                                       void* tmp, const float* mean, const float* stdv, int out_uint8, void* out,
+                                       void* stream) {
+  return resample_launch(B, S, rows_max, nullptr, desc, tables, tmp, mean, stdv, out_uint8, out, stream);
+}
+
+extern "C" int clipk_resample_tables(int B, int S, const long long* params, int* tables, void* stream) {
+  if (!params || !tables) return CLIPK_EINVAL;
+  if (B < 0 || S <= 0) return CLIPK_ESHAPE;
+  if (B == 0) return CLIPK_OK;
+  const long long n = (long long)B * 2 * S;
+  hipLaunchKernelGGL(resample_tables_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B,
+                     S, params, tables);
+  CLIPK_CHECK_LAUNCH();
+  return CLIPK_OK;
+}
+
+// The host twin: the same header functions in a plain loop, on host pointers; checks every record
+// before it writes anything.
+extern "C" int clipk_resample_tables_host(int B, int S, const long long* params, int* tables, void* stream) {
+  (void)stream;
+  if (!params || !tables) return CLIPK_EINVAL;
+  if (B < 0 || S <= 0) return CLIPK_ESHAPE;
+  for (int b = 0; b < B; ++b) {
+    const long long* q = params + (size_t)b * CLIPK_RESAMPLE_PARAMS;
+    if (q[10] < 1 || q[10] > S) return CLIPK_ESHAPE;
+    for (int v = 0; v < 2; ++v) {
+      const long long* p = q + (v ? 5 : 0);
+      if (p[0] < 1 || p[0] > INT32_MAX || p[1] < 1 || p[1] > INT32_MAX || p[2] < 0 || p[2] + q[10] > p[1] || p[3] < 0)
+        return CLIPK_ESHAPE;
+      if (p[4] != resample::make_axis((int)p[0], (int)p[1]).ksize) return CLIPK_ESHAPE;
+    }
+  }
+  for (int b = 0; b < B; ++b) {
+    const long long* q = params + (size_t)b * CLIPK_RESAMPLE_PARAMS;
+    for (int v = 0; v < 2; ++v) {
+      const long long* p = q + (v ? 5 : 0);
+      const int ks = (int)p[4];
+      const resample::Axis a = resample::make_axis((int)p[0], (int)p[1]);
+      for (int r = 0; r < (int)q[10]; ++r)
+        resample::table_row(a, (int)p[2] + r, v ? (int)q[11] : 0, ks, tables + p[3] + (size_t)r * (2 + ks));
+    }
+  }
   return CLIPK_OK;
 }
 

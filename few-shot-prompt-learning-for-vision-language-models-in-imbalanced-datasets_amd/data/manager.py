@@ -10,7 +10,10 @@ num_classes) -- the readers and few-shot / long-tail splits of data/fewshot.py b
 The image path: worker processes decode the files (PIL, RGB, as read_image does) into
 uint8 arrays; the main process runs the transforms on the GPU (data/preprocess.py, the
 CoOp/CoCoOp configs' random_resized_crop / random_flip / normalize for training and
-resize / center_crop / normalize for test) and yields device tensors.
+resize / center_crop / normalize for test) and yields device tensors. With NATIVE.IMAGE_BANK
+the decoded training images stay on the device after their first use (data/image_bank.py): the
+same DataLoader keeps running over a wrapper that skips the read of a banked image, so the
+sampler stream, the loader's own per-epoch seed draw and every other RNG are consumed as before.
 
 Multi-GPU (one process per GPU): the training sampler is built exactly as Dassl builds it
 (data/fewshot.py build_sampler: RandomSampler / WeightedClassSampler /
@@ -111,11 +114,14 @@ class _RangeSampler(Sampler):
 
 
 class DatasetWrapper(Dataset):
-    """data_manager.py:202-275 up to the decoded image (transforms run on the GPU)."""
+    """data_manager.py:202-275 up to the decoded image (transforms run on the GPU). banked (a
+    shared-memory bool tensor over the data source, ImageBank.banked): an index it marks is not
+    read -- "img" is None and the loader takes the pixels from the bank."""
 
-    def __init__(self, data_source, reader=read_image):
+    def __init__(self, data_source, reader=read_image, banked=None):
         self.data_source = data_source
         self.reader = reader
+        self.banked = banked
 
     def __len__(self):
         return len(self.data_source)
@@ -123,7 +129,8 @@ class DatasetWrapper(Dataset):
     def __getitem__(self, key):
         idx, n_global, n_local = key if isinstance(key, tuple) else (key, 0, 0)
         item = self.data_source[idx]
-        return {"img": self.reader(item.impath), "label": item.label, "domain": item.domain,
+        img = None if self.banked is not None and bool(self.banked[idx]) else self.reader(item.impath)
+        return {"img": img, "label": item.label, "domain": item.domain,
                 "impath": item.impath, "index": idx, "n_global": n_global, "n_local": n_local}
 
 
@@ -174,15 +181,20 @@ class GpuLoader:
     preprocessing output), "img" an alias of "img1" (the same tensor). mixup_alpha (not None):
     every batch is mixed after the transform (draw_mix from the transform's generator, after the
     batch's crop draws; ops.mixup_images): "img" the mixed images, "y_a" (= "label", kept) and
-    "y_b" the two targets, "lam" a Python float."""
+    "y_b" the two targets, "lam" a Python float. bank (an ImageBank over the loader's data source):
+    every image of a batch goes through bank.fetch first -- a banked one (its "img" is None: the
+    wrapper skipped the read) becomes the bank's record, one seen for the first time is uploaded
+    into the bank, one past the cap stays a host array; the transform draws and launches as
+    without the bank. "img" of the yielded batch is the transformed tensor either way."""
 
-    def __init__(self, loader, transform, device, views=1, mixup_alpha=None):
+    def __init__(self, loader, transform, device, views=1, mixup_alpha=None, bank=None):
         if views not in (1, 2):
             raise ValueError(f"views must be 1 or 2, got {views}")
         if views == 2 and mixup_alpha is not None:
             raise ValueError("a two-view loader does not mix its batches")
         self.loader, self.transform, self.device, self.views = loader, transform, device, views
         self.mixup_alpha = None if mixup_alpha is None else float(mixup_alpha)
+        self.bank = bank
 
     def __len__(self):
         return len(self.loader)
@@ -190,11 +202,14 @@ class GpuLoader:
     def __iter__(self):
         for b in self.loader:
             out = dict(b)
+            imgs = b["img"]
+            if self.bank is not None:
+                imgs = [self.bank.fetch(i, im) for i, im in zip(b["index"].tolist(), imgs)]
             if self.views == 2:
-                out["img1"], out["img2"] = self.transform(b["img"], views=2)
+                out["img1"], out["img2"] = self.transform(imgs, views=2)
                 out["img"] = out["img1"]
             else:
-                out["img"] = self.transform(b["img"])
+                out["img"] = self.transform(imgs)
             out["label"] = b["label"].to(self.device, non_blocking=True)
             if self.mixup_alpha is not None:
                 lam, perm = draw_mix(self.mixup_alpha, out["img"].shape[0], getattr(self.transform, "generator", None))
@@ -217,12 +232,21 @@ class DataManager:
         sampler = build_sampler(cfg.DATALOADER.TRAIN_X.SAMPLER, cfg=cfg, data_source=train, batch_size=bs)
         self.train_batch_sampler = ShardedBatchSampler(sampler, bs, drop_last=len(train) >= bs * world,
                                                        rank=rank, world=world)
+        # NATIVE.IMAGE_BANK: this rank's bank of the training images it touches (the cap is per rank)
+        native = cfg.get("NATIVE", {})
+        self.image_bank = None
+        if bool(native.get("IMAGE_BANK", False)):
+            from .image_bank import ImageBank
+            self.image_bank = ImageBank(len(train), self.device,
+                                        max_bytes=int(float(native.get("IMAGE_BANK_MAX_GB", 16)) * (1 << 30)))
+        banked = None if self.image_bank is None else self.image_bank.banked
         self.train_loader_x = GpuLoader(
-            DataLoader(DatasetWrapper(train, reader), batch_sampler=self.train_batch_sampler, num_workers=nw,
+            DataLoader(DatasetWrapper(train, reader, banked), batch_sampler=self.train_batch_sampler, num_workers=nw,
                        collate_fn=_collate, pin_memory=False),
             GpuTransform(cfg, is_train=True, device=self.device, generator=augment_generator(self.replicated)),
             self.device, views=2 if two_views(cfg) else 1,
-            mixup_alpha=float(cfg.TRAINER.IVLP.get("MIXUP_ALPHA", 1.0)) if mixup(cfg) else None)
+            mixup_alpha=float(cfg.TRAINER.IVLP.get("MIXUP_ALPHA", 1.0)) if mixup(cfg) else None,
+            bank=self.image_bank)
 
         def test_loader(data):
             if not data:

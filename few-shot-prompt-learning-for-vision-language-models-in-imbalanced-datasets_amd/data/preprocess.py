@@ -320,8 +320,52 @@ def _tables(plans, shapes):
     return np.asarray(desc, np.int64), np.concatenate(tabs).astype(np.int32), tmp_off
 
 
+def axis_taps(in_size, out_size, xx):
+    """resample_coeffs' (ksize, xmin[xx], xmax[xx]) of one output index in Python floats: the same
+    IEEE double operations in the same order, int() for C's truncation."""
+    scale = float(in_size) / out_size
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    center = (xx + 0.5) * scale
+    xmin = max(int(center - support + 0.5), 0)
+    xmax = min(int(center + support + 0.5), in_size) - xmin
+    return int(math.ceil(support)) * 2 + 1, xmin, xmax
+
+
+def _table_params(plans, shapes):
+    """_tables without the tables: the same descriptors (int64 [B, 16]) and temp size, plus the
+    records clipk_resample_tables builds the block from (int64 [B, RESAMPLE_PARAMS]) and the
+    block's size in ints. Scalar work only: center, xmin and xmin + xmax are nondecreasing in the
+    output index, so the temp rows start at the first v row's xmin and end at the last one's
+    xmin + xmax."""
+    desc = np.zeros((len(plans), 16), np.int64)
+    par = np.zeros((len(plans), N.RESAMPLE_PARAMS), np.int64)
+    tmp_off = tab_off = 0
+    for b, (p, (H, W)) in enumerate(zip(plans, shapes)):
+        hks = axis_taps(p.w, p.rw, 0)[0]
+        vks, ty0, _ = axis_taps(p.h, p.rh, p.oy)
+        _, ylast, nlast = axis_taps(p.h, p.rh, p.oy + p.S - 1)
+        rows = max(ylast + nlast - ty0, 1)
+        v_off = tab_off + p.S * (2 + hks)
+        desc[b] = (0, W, p.x0, p.y0 + ty0, p.S, int(p.flip), tab_off, hks, v_off, vks, tmp_off, rows, H, 0, 0, 0)
+        par[b] = (p.w, p.rw, p.ox, tab_off, hks, p.h, p.rh, p.oy, v_off, vks, p.S, ty0)
+        tab_off = v_off + p.S * (2 + vks)
+        tmp_off += rows * p.S * 3
+    return desc, par, tab_off, tmp_off
+
+
+class Resident:
+    """A decoded image that already lies in device memory (data/image_bank.py): the address of its
+    first byte, uint8 HWC, rows packed. Stands where preprocess_batch takes an image; `keep` holds
+    whatever owns the memory."""
+
+    def __init__(self, address, H, W, keep=None):
+        self.address, self.keep = int(address), keep
+        self.shape = (int(H), int(W), 3)
+
+
 def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8=False, src_index=None,
-                     color=None, blur=None):
+                     color=None, blur=None, tables="host"):
     """images: list of uint8 HWC (RGB) numpy arrays or CPU/GPU torch tensors; plans: Plan
     per image (all with the same S). Returns fp32 [B, 3, S, S] normalised on `device` (or
     the uint8 resampled pixels [B, 3, S, S] when out_uint8, for bit-exact checks).
@@ -331,14 +375,21 @@ def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8
     non-empty the resample writes uint8 and clipk_image_color writes the output (one more launch);
     None or all empty: the resample kernel writes the output itself, as without the argument.
     blur: one sigma or None per plan, GaussianBlur(radius=sigma) after the colour program, in the
-    colour launch (clipk_image_color_blur; color_batch). None or all None: as without the argument."""
+    colour launch (clipk_image_color_blur; color_batch). None or all None: as without the argument.
+    tables: "host" (the coefficient tables come from _tables and are uploaded) or "device"
+    (clipk_resample_tables builds the same block on the GPU from one record per plan; descriptors,
+    records and mean / std travel in ONE non-blocking copy from pinned memory). The same bits.
+    An image may be a Resident (pixels already on the device, read where they lie); with any the
+    launch is clipk_image_resample_at and only the other images are uploaded."""
     dev = torch.device(device)
+    if tables not in ("host", "device"):
+        raise ValueError(f'tables must be "host" or "device", got {tables!r}')
     S = plans[0].S
     if any(p.S != S for p in plans):
         raise ValueError("all plans must share the output size")
-    ts = [torch.as_tensor(im) for im in images]
+    ts = [im if isinstance(im, Resident) else torch.as_tensor(im) for im in images]
     for t in ts:
-        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+        if not isinstance(t, Resident) and (t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3):
             raise ValueError("images must be uint8 [H, W, 3]")
     color = None if color is None else [list(c) for c in color]
     if color is not None and len(color) != len(plans):
@@ -357,21 +408,53 @@ def preprocess_batch(images, plans, mean=MEAN, std=STD, device="cuda", out_uint8
     for p, (H, W) in zip(plans, shapes):
         if p.x0 < 0 or p.y0 < 0 or p.x0 + p.w > W or p.y0 + p.h > H or p.rw < p.ox + S or p.rh < p.oy + S:
             raise ValueError("plan window outside the image")
-    desc, tab, tmp_elems = _tables(plans, shapes)
-    offs = np.cumsum([0] + [H * W * 3 for H, W in img_shapes])
-    desc[:, 0] = offs[:-1][src_index]
-    src = torch.cat([t.reshape(-1) for t in ts]).to(dev, non_blocking=True)
-    d_desc = torch.from_numpy(desc).to(dev)
-    d_tab = torch.from_numpy(tab).to(dev)
-    tmp = torch.empty(max(tmp_elems, 1), dtype=torch.uint8, device=dev)
+        if tables == "device" and (p.w < 1 or p.h < 1 or p.ox < 0 or p.oy < 0 or S < 1):
+            raise ValueError("plan window outside the image")
+    if tables == "host":
+        desc, tab, tmp_elems = _tables(plans, shapes)
+    else:
+        desc, par, tab_elems, tmp_elems = _table_params(plans, shapes)
+    # the uploaded images, packed; a Resident stays where it is
+    host = [k for k, t in enumerate(ts) if not isinstance(t, Resident)]
+    offs = np.zeros(len(ts) + 1, np.int64)
+    offs[1:][host] = [img_shapes[k][0] * img_shapes[k][1] * 3 for k in host]
+    offs = np.cumsum(offs)
+    src = torch.cat([ts[k].reshape(-1) for k in host]).to(dev, non_blocking=True) if host else None
+    absolute = len(host) < len(ts)
+    if absolute:
+        base = src.data_ptr() if host else 0
+        addr = np.asarray([t.address if isinstance(t, Resident) else base + int(o) for t, o in zip(ts, offs[:-1])],
+                          np.int64)
+        desc[:, 0] = addr[src_index]
+    else:
+        desc[:, 0] = offs[:-1][src_index]
     B = len(plans)
+    if tables == "host":
+        d_desc = torch.from_numpy(desc).to(dev)
+        d_tab = torch.from_numpy(tab).to(dev)
+        mean_t = torch.tensor(mean, dtype=torch.float32, device=dev)
+        std_t = torch.tensor(std, dtype=torch.float32, device=dev)
+    else:
+        nd, npar = desc.size, par.size
+        stage = torch.empty(nd + npar + 3, dtype=torch.int64, pin_memory=True)
+        sn = stage.numpy()
+        sn[:nd], sn[nd:nd + npar] = desc.ravel(), par.ravel()
+        sn[nd + npar:].view(np.float32)[:] = tuple(mean) + tuple(std)
+        d_stage = stage.to(dev, non_blocking=True)
+        d_desc, d_par = d_stage[:nd], d_stage[nd:nd + npar]
+        mean_t, std_t = d_stage[nd + npar:].view(torch.float32).split(3)
+        d_tab = torch.empty(max(tab_elems, 1), dtype=torch.int32, device=dev)
+        N.call("clipk_resample_tables", B, S, ops._p(d_par), ops._p(d_tab), ops._stream())
+    tmp = torch.empty(max(tmp_elems, 1), dtype=torch.uint8, device=dev)
     to_u8 = out_uint8 or staged
     out = torch.empty(B, 3, S, S, device=dev, dtype=torch.uint8 if to_u8 else torch.float32)
-    mean_t = torch.tensor(mean, dtype=torch.float32, device=dev)
-    std_t = torch.tensor(std, dtype=torch.float32, device=dev)
     rows_max = int(desc[:, 11].max())
-    N.call("clipk_image_resample", B, S, rows_max, ops._p(src), ops._p(d_desc), ops._p(d_tab), ops._p(tmp),
-           ops._p(mean_t), ops._p(std_t), 1 if to_u8 else 0, ops._p(out), ops._stream())
+    if absolute:
+        N.call("clipk_image_resample_at", B, S, rows_max, ops._p(d_desc), ops._p(d_tab), ops._p(tmp),
+               ops._p(mean_t), ops._p(std_t), 1 if to_u8 else 0, ops._p(out), ops._stream())
+    else:
+        N.call("clipk_image_resample", B, S, rows_max, ops._p(src), ops._p(d_desc), ops._p(d_tab), ops._p(tmp),
+               ops._p(mean_t), ops._p(std_t), 1 if to_u8 else 0, ops._p(out), ops._stream())
     if staged:
         return color_batch(out, color if color is not None else [[]] * B, mean, std, out_uint8, blur)
     return out
@@ -413,6 +496,8 @@ class GpuTransform:
         self.std = tuple(cfg.INPUT.PIXEL_STD) if norm else (1.0, 1.0, 1.0)
         self.device = device
         self.generator = generator  # None: torch's global CPU RNG
+        # NATIVE.DEVICE_TABLES: the resample tables are built on the GPU (preprocess_batch tables="device")
+        self.tables = "device" if bool(cfg.get("NATIVE", {}).get("DEVICE_TABLES", False)) else "host"
         # colour stage (training only): jitter ranges (None: no jitter), the RandomApply probability
         # around it (>= 1: no coin is drawn) and RandomGrayscale's probability (None: not configured)
         self.jitter, self.jitter_p, self.gray_p = None, 1.0, None
@@ -480,17 +565,18 @@ class GpuTransform:
         """views=1: the transformed batch [B, 3, S, S]. views=2 (SimCLR): two independent draws of
         the transform per image -> (x1, x2), the two halves of ONE [2B, 3, S, S] output (no copy);
         the pixels are uploaded once and one resample launch (and, with colour ops or blur, one
-        colour / blur launch) covers both views."""
+        colour / blur launch) covers both views. An image may be a preprocess.Resident (an image
+        bank's record): its size is the recorded one and its pixels are read where they lie."""
         sizes = [(int(im.shape[1]), int(im.shape[0])) for im in images]
         if views == 1:
             drawn = self.plans(sizes)
             return preprocess_batch(images, drawn, self.mean, self.std, self.device, color=[p.color for p in drawn],
-                                    blur=[p.blur for p in drawn])
+                                    blur=[p.blur for p in drawn], tables=self.tables)
         if views != 2:
             raise ValueError(f"views must be 1 or 2, got {views}")
         B = len(sizes)
         drawn = self.plans(sizes, 2)  # image-major
         drawn = drawn[0::2] + drawn[1::2]
         out = preprocess_batch(images, drawn, self.mean, self.std, self.device, src_index=list(range(B)) * 2,
-                               color=[p.color for p in drawn], blur=[p.blur for p in drawn])
+                               color=[p.color for p in drawn], blur=[p.blur for p in drawn], tables=self.tables)
         return out[:B], out[B:]

@@ -202,6 +202,17 @@ def get_cfg_default() -> CfgNode:
                    # call (clipk_ce_loss_mix). Off: no loader mixes (USE_MIXUP alone changes nothing),
                    # and a batch that carries the mix keys takes the two-call branch as before
                    "MIXUP": False,
+                   # DEVICE_TABLES: the bicubic coefficient tables of every GPU transform (training and
+                   # test) are built on the GPU (clipk_resample_tables) from one record per view, and
+                   # descriptors and records go up in one non-blocking copy from pinned memory. The
+                   # same pixels, bit for bit. Off: numpy float64 tables per view, uploaded
+                   "DEVICE_TABLES": False,
+                   # IMAGE_BANK: the decoded TRAINING images stay on the GPU after their first use
+                   # (data/image_bank.py, at most IMAGE_BANK_MAX_GB GiB per rank, no eviction): from
+                   # the second epoch on a banked image is neither decoded nor uploaded, the resample
+                   # reads it where it lies. Same batches, same RNG streams. Off: every epoch decodes
+                   # and uploads every image
+                   "IMAGE_BANK": False, "IMAGE_BANK_MAX_GB": 16,
                    # FUSED_SRC: PromptSRC's head -- the feature normalisations, both logit products,
                    # CE / focal, the two L1 terms, the KL term, their weights and all of their
                    # backward -- as one native call on the raw encoder outputs (clipk_src_head), where

@@ -241,6 +241,36 @@ int clipk_image_resample(int B, int S, int rows_max, const void* src, const long
                          const int* tables, void* tmp, const float* mean, const float* stdv,
                          int out_uint8, void* out, void* stream);
 
+/* clipk_image_resample on images that stay where they lie: desc[0] of every image is the ABSOLUTE
+ * device address of its first byte (an image bank's chunk, an upload buffer, or both in one batch),
+ * so there is no src argument. The same two kernels, arithmetic, desc and tables otherwise. The
+ * caller checks every window against the image's rows and row stride: the kernels read
+ * desc[0] + ((desc[3] + r) * desc[1] + desc[2] + tap) * 3 + c without a bound of their own. */
+int clipk_image_resample_at(int B, int S, int rows_max, const long long* desc, const int* tables, void* tmp,
+                            const float* mean, const float* stdv, int out_uint8, void* out, void* stream);
+
+/* The coefficient tables of clipk_image_resample, built on the device (csrc/resample_ops.h: Pillow's
+ * precompute_coeffs + normalize_coeffs_8bpc for the bicubic filter, every step in double and in
+ * Pillow's order, the sum of a row's taps taken tap after tap by one thread). params: DEVICE int64
+ * [B, CLIPK_RESAMPLE_PARAMS], per image
+ *   [0] window width w, [1] resized width rw, [2] output window origin ox, [3] h-table offset,
+ *   [4] h ksize, [5] window height h, [6] resized height rh, [7] oy, [8] v-table offset, [9] v ksize,
+ *   [10] S (rows per table, <= the argument S), [11] ty0 (subtracted from the v rows' first tap).
+ * Writes into tables (int32, offsets in ints: desc[6] / desc[8] of clipk_image_resample) per image
+ * S h rows for the outputs ox .. ox + S - 1 of w -> rw and S v rows for oy .. oy + S - 1 of h -> rh,
+ * each (first tap, taps used, ksize coefficients, zero past the taps used): the block
+ * fsp_amd/data/preprocess.py _tables builds on the host, bit for bit. ksize must be the
+ * filter's 2 * ceil(2 * max(in / out, 1)) + 1 of its axis (a row never has more taps); it is the
+ * caller's to compute, as the row stride bounds every write. One thread per row, B * 2 * S rows.
+ * CLIPK_EINVAL: a null pointer; CLIPK_ESHAPE: B < 0, S <= 0. B == 0: CLIPK_OK, nothing launched.
+ * clipk_resample_tables_host: the same arguments with HOST pointers (stream ignored), the same
+ * header functions in a plain loop; it also checks every record (extents >= 1, 0 <= origin,
+ * origin + S <= resized extent, S within 1..argument S, ksize the filter's, offsets >= 0) and
+ * returns CLIPK_ESHAPE before writing anything when one fails. */
+enum { CLIPK_RESAMPLE_PARAMS = 12 };
+int clipk_resample_tables(int B, int S, const long long* params, int* tables, void* stream);
+int clipk_resample_tables_host(int B, int S, const long long* params, int* tables, void* stream);
+
 /* Colour augmentations on the resampled pixels (torchvision ColorJitter / RandomGrayscale on PIL
  * images, i.e. Pillow's ImageEnhance.Brightness / Contrast / Color, convert("HSV") and convert("L");
  * csrc/preprocess.hip "colour stage", DESIGN §3 "Colour kernels"): every uint8 result is Pillow's.
